@@ -35,6 +35,13 @@ kernel's mean duration from HIP events on its launch stream.  peak = 8 TB/s HBM.
 The kernel is bound by its dependent node-fetch chain (latency), not by HBM:
 `bound` says so and `hbm_frac` gives the PMC-measured fabric bytes' fraction.
 cpu_baseline: the strict-IEEE C oracle (oracle/, "port") on the host cores.
+
+A plain run sets up, warms up, times --steps steps and prints the result line
+(metric, value, unit, higher_is_better, dtype, ms_per_step, ...).  The roofline,
+the CPU baseline and every other figure or check described above and reported
+beside value are measured only with --full, after the timed steps.
+--dump-outputs DIR writes what the last timed step left in its output buffers
+as DIR/<name>.npy (capture_outputs).
 """
 import argparse
 import ctypes
@@ -99,7 +106,19 @@ def parse():
     p.add_argument("--display-share", type=float, default=None,
                    help="N > 1: the display rank's share of a normal rank's bands (default: calibrated from its "
                         "assemble time; 1 = round-robin)")
-    p.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU-baseline time budget (0 = skip)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check everything reported beside value: the roofline (fetch counts, "
+                        "the render kernel's own time), the CPU baseline and its parity check, the shadow pass, "
+                        "other poses, the drop-in loops, frames / samples in flight, the band rehearsal and, at "
+                        "N > 1, the stage times, the assembled-frame checks, the other frame and the samples "
+                        "lines.  Without it a run sets up, warms up, times --steps steps and prints value")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step left to DIR/<name>.npy (float32 / "
+                        "float64, at most 64 MB in all; larger outputs as a fixed, seeded sample of pixels): "
+                        "rgba (the RGBA32F Result), hits (the hit-record fields of the pixels listed in "
+                        "sample_pixels; a miss's infinite t as -1) and, at N > 1, rgba8 (the display frame's "
+                        "words at sample_pixels)")
+    p.add_argument("--cpu-seconds", type=float, default=8.0, help="--full: CPU-baseline time budget (0 = skip)")
     p.add_argument("--no-rgba", action="store_true")
     p.add_argument("--camera", choices=["flyover", "overview", "main", "terrain"], default=None)
     p.add_argument("--shadows", action="store_true", help="C3 '+1 shadow ray' pass after the primary rays")
@@ -111,6 +130,8 @@ def parse():
                    help="svo_config field for the context (include/svo_rt.h; A/B runs): the policy only, every "
                         "setting renders the same frames")
     a = p.parse_args()
+    if a.steps < 1:
+        p.error("--steps: at least one timed step")
     a.svo_config = {}
     for kv in a.set:
         k, v = kv.split("=", 1)
@@ -155,6 +176,91 @@ def host_cpu_info():
     info["cgroup_cpu_quota"] = quota
     info["usable_cpus"] = max(1, min(avail, int(math.floor(quota)) if quota else avail))
     return info
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000   # --dump-outputs: all files together
+DUMP_WHOLE_PIXELS = 1 << 21           # the RGBA32F Result whole up to this many pixels (1920x1080: 33 MB)
+DUMP_SAMPLE_PIXELS = 1 << 18          # else, and for the hit records (8 float64 fields each), this many pixels
+DUMP_SEED = 0x5F0D
+
+
+def sample_pixels(n_px, cap=DUMP_SAMPLE_PIXELS):
+    """The pixels --dump-outputs samples: all of them up to `cap`, else a fixed, seeded, sorted choice."""
+    if n_px <= cap:
+        return np.arange(n_px, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, cap, replace=False)).astype(np.int64)
+
+
+def host_rows(t, n_px, idx=None):
+    """Records `idx` (None: all) of a device tensor of n_px equal-sized records, as a host (n, width) array."""
+    import torch
+    t = t.view(n_px, -1)
+    if idx is not None:
+        t = t[torch.as_tensor(idx, device=t.device)]
+    return t.cpu().numpy()
+
+
+def hit_fields(records):
+    """(n, 24) uint8 hit records -> (n, 8) float64, one column per svo_hit field (every field exact).
+    A miss's t (+inf in the record) is written as -1 so that every dumped value is finite and two
+    dumps can be subtracted; flags bit 0 and parent 0xFFFFFFFF still tell the miss."""
+    from raytracingtest_amd import _lib
+    h = np.ascontiguousarray(records).reshape(-1).view(_lib.HIT_DTYPE)
+    cols = np.stack([h[k].astype(np.float64) for k in _lib.HIT_DTYPE.names], axis=1)
+    cols[~np.isfinite(cols)] = -1.0
+    return cols
+
+
+def capture_outputs(n_px, hits=None, rgba=None, rgba8=None, prefix=""):
+    """Host copies of what a step left in its device output buffers (n_px records each), in the
+    --dump-outputs form: the Result whole when it fits, everything else at sample_pixels."""
+    idx = sample_pixels(n_px)
+    out = {prefix + "sample_pixels": idx.astype(np.float64)}
+    if hits is not None:
+        out[prefix + "hits"] = hit_fields(host_rows(hits, n_px, idx))
+    if rgba is not None:
+        out[prefix + "rgba"] = host_rows(rgba, n_px, None if n_px <= DUMP_WHOLE_PIXELS else idx)
+    if rgba8 is not None:
+        out[prefix + "rgba8"] = host_rows(rgba8, n_px, idx).view(np.uint32).astype(np.float64)
+    return out
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 or float64."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, over the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def workload_name(args, W, H):
+    kind = "Menger" if args.svo == "menger" else "Custom1"
+    return (f"{args.config} depth-{args.max_level - 1} ({1 << (args.max_level - 1)}^3) {kind} SVO, "
+            f"{W}x{H} primary rays" + (" + 1 shadow ray per hit" if args.shadows else "") +
+            f", {args.camera} camera")
+
+
+def result_head(args, rays_per_step, ms_per_step, world, scaling):
+    """The result line's fields that every run reports, --full or not."""
+    return {
+        "metric": METRIC,
+        "value": round(rays_per_step / (ms_per_step * 1e-3) / 1e6, 2),
+        "unit": "Mrays/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4),
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "full": bool(args.full),
+        "data": ("synthetic: 256^3 Menger sponge surface SVO (SURVEY.md 8(d) C2)" if args.svo == "menger" else
+                 "synthetic: Custom1 OpenSimplex(seed 7) terrain SVO built on-GPU by the NaiveCreator restatement"),
+    }
 
 
 def main():
@@ -229,7 +335,31 @@ def main():
     sptr = stream.cuda_stream
     preflight = rank_preflight(args, rank, world, dev, dist) if world > 1 else None
 
-    m = measure_frame(args, rm, W, H, rank, world, dev, stream, dist)
+    m = measure_frame(args, rm, W, H, rank, world, dev, stream, dist, dump=True)
+    if m["captured"] is not None:
+        write_outputs(args.dump_outputs, m["captured"])
+    if not args.full:
+        if rank == 0:
+            ms_per_step = m["elapsed"] / args.steps * 1e3
+            out = result_head(args, W * H, ms_per_step, world, scaling)
+            weighted = bool(m["deal_info"] and m["deal_info"]["cycle_bands"])
+            out["config"] = {"workload": workload_name(args, W, H), "svo_config": args.svo_config or "defaults",
+                             "svo_nodes": n_nodes, "svo_format": "V%d" % svo.format, "build_s": round(build_s, 2),
+                             "stack_mode": "hlsl" if args.stack_mode == 0 else "exact",
+                             "rays_per_step": W * H, "rays_per_gpu_step": m["n_px"],
+                             "parallelism": ("single" if world == 1 else
+                                             f"bands{world}x8rows{'-weighted' if weighted else ''}"
+                                             f"+rccl_gather({args.payload})")}
+            out["gpu_span_ms_per_step"] = round(m["span_ms"], 4)
+            if world > 1:
+                out["multi_gpu"] = {"frame": f"{W}x{H}", "band_rows": 8, "payload": args.payload,
+                                    "preflight": preflight, "display_rank_deal": m["deal_info"],
+                                    "payload_choice": m["payload_choice"]}
+            print(json.dumps(out), flush=True)
+        rm.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     gather, hits, rgba, n_px, n_hit, F, host_hits = (m["gather"], m["hits"], m["rgba"], m["n_px"], m["n_hit"],
                                                       m["F"], m["host_hits"])
     band, deal_info, payload_choice = m["band"], m["deal_info"], m["payload_choice"]
@@ -321,15 +451,11 @@ def main():
 
     rays_per_step = W * H
     ms_per_step = elapsed / args.steps * 1e3
-    mrays = rays_per_step / (ms_per_step * 1e-3) / 1e6
     achieved = bytes_per_launch / (kern_ms * 1e-3) / 1e9
 
     if rank == 0:
         cpu = cpu_baseline(args, svo, cam, host_hits) if (world == 1 and args.cpu_seconds > 0) else None
-        kind = "Menger" if args.svo == "menger" else "Custom1"
-        workload = (f"{args.config} depth-{args.max_level - 1} ({1 << (args.max_level - 1)}^3) {kind} SVO, "
-                    f"{W}x{H} primary rays" + (" + 1 shadow ray per hit" if args.shadows else "") +
-                    f", {args.camera} camera")
+        workload = workload_name(args, W, H)
         from raytracingtest_amd.build import source_digest
         digest = source_digest()
         pmc = pmc_traffic(workload, digest) if band is None else None
@@ -337,20 +463,8 @@ def main():
         weighted = bool(deal_info and deal_info["cycle_bands"])
         par = ("single" if world == 1 else
                f"bands{world}x8rows{'-weighted' if weighted else ''}+rccl_gather({args.payload})")
-        out = {
-            "metric": METRIC,
-            "value": round(mrays, 2),
-            "unit": "Mrays/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(ms_per_step, 4),
-            "higher_is_better": True,
-            "scaling": scaling,
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": ("synthetic: 256^3 Menger sponge surface SVO (SURVEY.md 8(d) C2)" if args.svo == "menger" else
-                     "synthetic: Custom1 OpenSimplex(seed 7) terrain SVO built on-GPU by the NaiveCreator restatement"),
+        out = result_head(args, rays_per_step, ms_per_step, world, scaling)
+        out.update({
             "config": {"workload": workload, "svo_config": args.svo_config or "defaults",
                        "svo_nodes": n_nodes, "svo_format": "V%d" % svo.format, "svo_leaves": getattr(svo, "n_leaves", None),
                        "build_s": round(build_s, 2), "stack_mode": "hlsl" if args.stack_mode == 0 else "exact",
@@ -412,7 +526,7 @@ def main():
                          "traffic_source": None if pmc is None else pmc.get("source")},
             "cpu_baseline": cpu,
             "c3_plus_shadow_ray": shadow,
-        }
+        })
         if world > 1:
             out["multi_gpu"] = {
                 "frame": f"{W}x{H}", "band_rows": 8, "payload": args.payload,
@@ -451,7 +565,7 @@ def main():
         dist.destroy_process_group()
 
 
-def measure_frame(args, rm, W, H, rank, world, dev, stream, dist):
+def measure_frame(args, rm, W, H, rank, world, dev, stream, dist, dump=False):
     """One measured frame size: the instrumented fetch count, warmup, K timed steps
     between barrier + synchronize, K more steps with the render kernel bracketed by
     library HIP events, and (N > 1) the serialized stage times and the assembled-frame
@@ -485,15 +599,16 @@ def measure_frame(args, rm, W, H, rank, world, dev, stream, dist):
         if gather is not None:
             gather.drain()
 
-    # instrumented pass (outside the timed region): per-ray fetch counts
-    fetch = torch.zeros(max(n_px, 1), dtype=torch.int32, device=dev)
-    rm.count_fetches_device(W, H, fetch.data_ptr(), stack_mode=args.stack_mode, band=band, stream=sptr)
-    # ... and of the walk the render runs (from the beam start): the node reads the
-    # kernel actually makes, the `frac` accounting; the reference's walk above gives frac_reference_work
-    fetch_run = torch.zeros_like(fetch)
-    rm.set_count_beam(True)
-    rm.count_fetches_device(W, H, fetch_run.data_ptr(), stack_mode=args.stack_mode, band=band, stream=sptr)
-    rm.set_count_beam(False)
+    # --full: instrumented pass (outside the timed region): per-ray fetch counts
+    if args.full:
+        fetch = torch.zeros(max(n_px, 1), dtype=torch.int32, device=dev)
+        rm.count_fetches_device(W, H, fetch.data_ptr(), stack_mode=args.stack_mode, band=band, stream=sptr)
+        # ... and of the walk the render runs (from the beam start): the node reads the
+        # kernel actually makes, the `frac` accounting; the reference's walk above gives frac_reference_work
+        fetch_run = torch.zeros_like(fetch)
+        rm.set_count_beam(True)
+        rm.count_fetches_device(W, H, fetch_run.data_ptr(), stack_mode=args.stack_mode, band=band, stream=sptr)
+        rm.set_count_beam(False)
     for _ in range(max(1, args.warmup)):
         step()
     drain()
@@ -532,6 +647,24 @@ def measure_frame(args, rm, W, H, rank, world, dev, stream, dist):
         dist.barrier()
     elapsed = time.perf_counter() - t_start
     step_ms = float(np.mean([a.elapsed_time(b) for a, b in ev])) if step_events else None
+    span_ms = span0.elapsed_time(span1) / span_n
+    # --dump-outputs: what the last timed step left (rank 0: the display frame and its own bands' records)
+    captured = None
+    if dump and args.dump_outputs and rank == 0:
+        if gather is None:
+            captured = capture_outputs(n_px, hits=hits, rgba=rgba)
+        else:
+            captured = capture_outputs(W * H, rgba8=gather.frame8[gather.last])
+            captured.update(capture_outputs(n_px, hits=gather.local_hits(), prefix="rank0_"))
+    if not args.full:
+        # a plain run ends here: value's timed steps, and the GPU span per launch they leave for free
+        if world > 1:
+            t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            elapsed = float(t[0])
+        return dict(gather=gather, hits=hits, rgba=rgba, n_px=n_px, band=band, deal_info=deal_info,
+                    payload_choice=payload_choice, elapsed=elapsed, step_ms=step_ms, step=step, span_ms=span_ms,
+                    captured=captured)
     # the roofline's kernel time: the primary-ray kernel's own mean duration, from
     # HIP events the library records on the launch stream around that kernel
     # alone (SVO_OPT_KERNEL_TIMING), over K more steps of the same workload right
@@ -551,7 +684,6 @@ def measure_frame(args, rm, W, H, rank, world, dev, stream, dist):
     # it belongs to): the same two hipEventRecords around a one-element kernel on the same stream
     floor_ms = event_floor_ms(stream, dev)
     kern_ms_bracket = max(kern_ms_events - floor_ms, 1e-6)
-    span_ms = span0.elapsed_time(span1) / span_n
     # N = 1: the timed region's GPU span per launch (only the render kernel runs on the stream at a
     # held view: the beam splat and the order builds happened in the warmup); N > 1: the bracketed
     # kernel (the steps also hold the gather)
@@ -583,7 +715,7 @@ def measure_frame(args, rm, W, H, rank, world, dev, stream, dist):
                 deal_info=deal_info, payload_choice=payload_choice, bytes_per_launch=bytes_per_launch,
                 elapsed=elapsed, kern_ms=kern_ms, kern_ms_max=kern_ms_max, stages=stages, frame_check=frame_check,
                 per_rank=per_rank, step_ms=step_ms, step=step, kern_ms_events=kern_ms_events, floor_ms=floor_ms,
-                kern_ms_bracket=kern_ms_bracket, span_ms=span_ms)
+                kern_ms_bracket=kern_ms_bracket, span_ms=span_ms, captured=captured)
 
 
 def event_floor_ms(stream, dev, n=200):
@@ -1197,7 +1329,7 @@ def bench_multidevice(args, svo, cam, W, H, scaling, build_s):
         for d in distinct:
             torch.cuda.synchronize(d)
 
-    def measure(Wf, Hf):
+    def measure(Wf, Hf, dump=False):
         rm.UpdateShaderParameters(cam, Wf, Hf)
         hits = torch.empty(Wf * Hf * 24, dtype=torch.uint8, device=dev0)
         rgba = None if args.no_rgba else torch.empty(Wf * Hf * 4, dtype=torch.float32, device=dev0)
@@ -1239,6 +1371,10 @@ def bench_multidevice(args, svo, cam, W, H, scaling, build_s):
             step()
         sync_all()
         elapsed = time.perf_counter() - t
+        ms = elapsed / args.steps * 1e3
+        captured = capture_outputs(Wf * Hf, hits=hits, rgba=rgba, rgba8=frame8) if dump and args.dump_outputs else None
+        if not args.full:
+            return {"ms": ms, "deal": deal, "captured": captured}
         rm.set_kernel_timing(True)
         rm.stage_time(0)
         rm.stage_time(1)
@@ -1278,9 +1414,8 @@ def bench_multidevice(args, svo, cam, W, H, scaling, build_s):
                  "rgba32f_mismatches": None if rgba is None else
                  int((w_rgba.view(-1, 4) != rgba.view(-1, 4)).any(1).sum().item())}
         one.close()
-        ms = elapsed / args.steps * 1e3
         return {"ms": ms, "kern": kern, "asm_ms": asm_ms, "deal": deal, "check": check, "bytes0": bytes0,
-                "F0": F, "rows0": rows0}
+                "F0": F, "rows0": rows0, "captured": captured}
 
     def measure_samples_md(S):
         """Samples in flight through the multi-device context (svo_render_samples): every
@@ -1325,7 +1460,18 @@ def bench_multidevice(args, svo, cam, W, H, scaling, build_s):
         return {"S": S, "ms_per_step": round(ms, 4), "Mrays_per_s": round(S * W * H / (ms * 1e-3) / 1e6, 2),
                 "assembled_frame_check": {"pixels": W * H, "samples_accumulated": cnt[0], "rgba8_mismatches": bad}}
 
-    r = measure(W, H)
+    r = measure(W, H, dump=True)
+    if r["captured"] is not None:
+        write_outputs(args.dump_outputs, r["captured"])
+    if not args.full:
+        rm.close()
+        out = result_head(args, W * H, r["ms"], n, scaling)
+        out["config"] = {"workload": workload_name(args, W, H),
+                         "parallelism": f"multidevice{n}x8rows+xgmi_pull(compact)", "build_s": round(build_s, 2),
+                         "svo_nodes": len(svo), "stack_mode": "hlsl" if args.stack_mode == 0 else "exact"}
+        out["multi_gpu"] = {"devices": args.device_list, "preflight": preflight, "display_device_deal": r["deal"]}
+        print(json.dumps(out), flush=True)
+        return
     samples_md = None
     if args.extras:
         samples_md = {"frame": f"{W}x{H}", "per_samples": [measure_samples_md(S) for S in (1, 2, 4, 8)],
@@ -1347,7 +1493,7 @@ def bench_multidevice(args, svo, cam, W, H, scaling, build_s):
     print(json.dumps({
         "metric": METRIC, "value": round(W * H / (ms * 1e-3) / 1e6, 2), "unit": "Mrays/s", "n_gpus": n,
         "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 4), "higher_is_better": True,
-        "scaling": scaling, "vs_baseline": None, "dtype": "f32",
+        "scaling": scaling, "vs_baseline": None, "dtype": "f32", "full": True,
         "data": ("synthetic: 256^3 Menger sponge surface SVO (SURVEY.md 8(d) C2)" if args.svo == "menger" else
                  "synthetic: Custom1 OpenSimplex(seed 7) terrain SVO built on-GPU by the NaiveCreator restatement"),
         "config": {"workload": (f"{args.config} depth-{args.max_level - 1} ({1 << (args.max_level - 1)}^3) {kind} SVO, "

@@ -1,4 +1,4 @@
-"""Generate tests/golden/c1_text_frames.npz: config C1 frames of
+"""Generate tests/golden/c1_text_frames_{main,overview}.npz (one file per camera): config C1 frames of
 the reference's `Text` SVO (tests/golden/text_svo.npz) -- 256x256 primary
 rays, Main.unity and overview cameras, HLSL and exact stack modes (one Result
 frame per camera: it is the same in both modes) -- traced by
@@ -47,4 +47,7 @@ def frames():
 
 
 if __name__ == "__main__":
-    np.savez_compressed(os.path.join(HERE, "c1_text_frames.npz"), **frames())
+    out = frames()
+    for cam_name in ("main", "overview"):
+        np.savez_compressed(os.path.join(HERE, f"c1_text_frames_{cam_name}.npz"),
+                            **{k: v for k, v in out.items() if k.startswith(cam_name + "_")})

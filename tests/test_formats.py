@@ -2,13 +2,15 @@
 
 * CompactSVO.SaveToDisk (CompactSVO.cs:80-86): raw little-endian int32
   descriptors, no header, no attachments;
-* the reference's `Text` debug dump (Assets/Scripts/SVO/CompactSVO/Text):
-  parsed by the product importer and compared with the committed fixture;
+* the reference's `Text` debug dump (Assets/Scripts/SVO/CompactSVO/Text, a data
+  file kept gzipped as tests/golden/reference_text_dump.gz): parsed by the
+  product importer and compared with the committed fixture;
 * the native SVOP pool file (header + nodes + attachments);
 * NaiveCreator.Create(root, getLeaf) linking (NaiveCreator.cs:30-42,156-159;
   Clipmap.cs:153-169): the product's link_leaves against the object-recursive
   restatement in oracle/naive_creator.py, bit for bit.
 """
+import gzip
 import os
 
 import numpy as np
@@ -17,7 +19,7 @@ import pytest
 from raytracingtest_amd.builder import build_menger, link_leaves
 from raytracingtest_amd.svo_data import SVOData, SVOFormatError
 
-TEXT_DUMP = "/root/reference/Assets/Scripts/SVO/CompactSVO/Text"
+TEXT_DUMP_GZ = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_text_dump.gz")
 
 
 def test_int32_dump_roundtrip_is_raw_little_endian(tmp_path, text_svo):
@@ -65,11 +67,13 @@ def test_svop_rejects_bad_files(tmp_path, text_svo):
         SVOData.load(str(tmp_path / "ver.svop"))
 
 
-@pytest.mark.skipif(not os.path.exists(TEXT_DUMP), reason="reference Text dump not present")
-def test_parse_text_dump_matches_fixture(text_fixture, text_svo):
+def test_parse_text_dump_matches_fixture(tmp_path, text_fixture, text_svo):
     """The product importer reads the reference's own file to the same pool as
     the committed fixture (tests/golden/make_text_fixture.py)."""
-    svo = SVOData.parse_text_dump(TEXT_DUMP)
+    dump = tmp_path / "Text"
+    with gzip.open(TEXT_DUMP_GZ, "rb") as fh:
+        dump.write_bytes(fh.read())
+    svo = SVOData.parse_text_dump(str(dump))
     assert len(svo) == 4977 and svo.format == 1
     assert np.array_equal(svo.to_v2(), text_svo.to_v2())
     assert np.array_equal(svo.attachments, text_svo.attachments)

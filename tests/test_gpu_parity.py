@@ -431,7 +431,7 @@ def test_c1_golden_frames(rm, text_svo, mode, camera_name):
     frames (tests/golden/make_c1_golden.py), without running the oracle."""
     import os
     from tests.conftest import GOLDEN
-    z = np.load(os.path.join(GOLDEN, "c1_text_frames.npz"))
+    z = np.load(os.path.join(GOLDEN, f"c1_text_frames_{camera_name}.npz"))
     key = f"{camera_name}_{'hlsl' if mode == 0 else 'exact'}"
     ref_hits = np.frombuffer(z[key + "_hits"].tobytes(), HIT_DTYPE)
     rm.SetSVOBuffer(text_svo)

@@ -295,7 +295,7 @@ def test_oracle_reproduces_c1_golden_frames(oracle_mod, text_svo, mode, camera_n
     golden vectors (tests/golden/make_c1_golden.py): a compiler, flag or code change
     that moves any bit of a hit record or Result pixel is caught here."""
     from raytracingtest_amd.camera import main_camera, main_light, overview_camera
-    z = np.load(os.path.join(GOLDEN, "c1_text_frames.npz"))
+    z = np.load(os.path.join(GOLDEN, f"c1_text_frames_{camera_name}.npz"))
     key = f"{camera_name}_{'hlsl' if mode == 0 else 'exact'}"
     cam = main_camera() if camera_name == "main" else overview_camera()
     c2w, inv_proj = cam.uniforms(256, 256)

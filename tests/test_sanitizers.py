@@ -4,6 +4,7 @@ ThreadSanitizer (its renderer is multithreaded), driven from a plain C process
 without shadow rays, two cameras.  The sanitized runs must report nothing and
 produce the same bytes as the regular oracle build."""
 import os
+import platform
 import shutil
 import subprocess
 
@@ -18,6 +19,19 @@ SAN = {
     "asan_ubsan": ["-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"],
     "tsan": ["-fsanitize=thread"],
 }
+# ThreadSanitizer's runtime maps its shadow at fixed addresses and stops with "unexpected memory
+# mapping" when the kernel's address-space randomisation (vm.mmap_rnd_bits above 28) puts the
+# program or a library outside the ranges it expects: the sanitized drivers run with the
+# randomisation off for their own process (setarch -R), where the host allows it
+SETARCH = shutil.which("setarch")
+
+
+def _no_aslr():
+    if SETARCH is None:
+        return []
+    prefix = [SETARCH, platform.machine(), "-R"]
+    ok = subprocess.run(prefix + ["true"], capture_output=True).returncode == 0
+    return prefix if ok else []
 
 
 @pytest.fixture(scope="module")
@@ -34,7 +48,7 @@ def drivers(tmp_path_factory):
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             pytest.skip(f"{name} toolchain unavailable: {r.stderr[-400:]}")
-        out[name] = exe
+        out[name] = _no_aslr() + [exe]
     return out
 
 
@@ -61,7 +75,7 @@ def test_oracle_clean_under_sanitizers(drivers, tmp_path, oracle_mod, text_svo, 
     ocam = _input(tmp_path / "in.bin", text_svo, cam, w, h, mode, oracle_mod)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1", UBSAN_OPTIONS="halt_on_error=1",
                TSAN_OPTIONS="halt_on_error=1")
-    r = subprocess.run([drivers[san], str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True,
+    r = subprocess.run([*drivers[san], str(tmp_path / "in.bin"), str(tmp_path / "out.bin")], capture_output=True,
                        text=True, env=env, timeout=120)
     assert r.returncode == 0 and "Sanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-2000:]
     raw = (tmp_path / "out.bin").read_bytes()

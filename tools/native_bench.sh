@@ -15,5 +15,5 @@ gcc -O2 -std=c99 -Wall -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include exam
     -Lraytracingtest_amd -lsvo_rt -lsvo_build -L/opt/rocm/lib -lamdhip64 -lm \
     -Wl,-rpath,$PWD/raytracingtest_amd -Wl,-rpath,/opt/rocm/lib -o "$OUT/bench_native"
 timeout -k 10 120 "$OUT/bench_native" 4 11 "$OUT/cam_flyover.bin" 1920 1080 1000 50 | tee "$OUT/native.json"
-timeout -k 10 300 python -u bench.py --no-extras --cpu-seconds 0 | tee "$OUT/bench_py.json"
+timeout -k 10 300 python -u bench.py --full --no-extras --cpu-seconds 0 | tee "$OUT/bench_py.json"
 timeout -k 10 120 "$OUT/bench_native" 4 11 "$OUT/cam_flyover.bin" 1920 1080 1000 50 | tee -a "$OUT/native.json"

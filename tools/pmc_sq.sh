@@ -9,7 +9,7 @@ for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE
            "SQ_WAVES SQ_INSTS_VMEM_RD SQ_INSTS_LDS SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_INSTS_SMEM SQ_WAIT_INST_LDS" \
            "TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE GRBM_COUNT"; do
   i=$((i+1))
-  timeout -k 10 120 rocprofv3 --pmc $grp --kernel-trace --kernel-include-regex "$RE" -d $OUT/g$i -o run --output-format csv -- python3 bench.py --steps 20 --warmup 400 --cpu-seconds 0 --no-extras > /dev/null 2>> $OUT/err.log || exit $?
+  timeout -k 10 120 rocprofv3 --pmc $grp --kernel-trace --kernel-include-regex "$RE" -d $OUT/g$i -o run --output-format csv -- python3 bench.py --full --steps 20 --warmup 400 --cpu-seconds 0 --no-extras > /dev/null 2>> $OUT/err.log || exit $?
 done
 python3 - "$OUT" <<'PY'
 import csv, glob, collections, json, sys

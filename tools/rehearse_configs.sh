@@ -13,9 +13,9 @@ OUT=gpurun_out/configs_multi
 mkdir -p $OUT
 export SVO_BENCH_BACKEND=gloo MASTER_ADDR=127.0.0.1
 timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 4 --master-addr 127.0.0.1 \
-  --master-port 29611 bench.py --gpus 4 --config C4 --steps 10 --warmup 2 > $OUT/c4_ranks4.json 2> $OUT/c4_ranks4.err || exit $?
+  --master-port 29611 bench.py --full --gpus 4 --config C4 --steps 10 --warmup 2 > $OUT/c4_ranks4.json 2> $OUT/c4_ranks4.err || exit $?
 tail -n 1 $OUT/c4_ranks4.json
-timeout -k 10 500 python bench.py --gpus 8 --devices 0,0,0,0,0,0,0,0 --config C5 --steps 10 --warmup 2 \
+timeout -k 10 500 python bench.py --full --gpus 8 --devices 0,0,0,0,0,0,0,0 --config C5 --steps 10 --warmup 2 \
   > $OUT/c5_md8.json 2> $OUT/c5_md8.err || exit $?
 tail -n 1 $OUT/c5_md8.json
 if [ "${C5_RANKS:-0}" = 1 ]; then
@@ -23,7 +23,7 @@ if [ "${C5_RANKS:-0}" = 1 ]; then
   ( while sleep 20; do date >> $OUT/heartbeat; done ) &
   hb=$!
   timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
-    --master-port 29612 bench.py --gpus 8 --config C5 --steps 5 --warmup 2 --payload rgb8 > $OUT/c5_ranks8.json 2> $OUT/c5_ranks8.err
+    --master-port 29612 bench.py --full --gpus 8 --config C5 --steps 5 --warmup 2 --payload rgb8 > $OUT/c5_ranks8.json 2> $OUT/c5_ranks8.err
   rc=$?
   kill $hb
   [ $rc = 0 ] || exit $rc
