@@ -19,7 +19,7 @@
  *    svo_forget_stream(ctx, stream), svo_synchronize(ctx) or svo_destroy(ctx):
  *    until one of them, the context may record an event on it (when a fifth
  *    stream takes its dispatch-order state over, or another stream takes the
- *    host-path scratch).  After svo_synchronize no work is pending anywhere, so
+ *    host-path scratch or the ordered ray query's scratch).  After svo_synchronize no work is pending anywhere, so
  *    the context records nothing on a stream it saw before that call.
  *  - policy (dispatch order, loop form, segmented rays, beam starts, shadow and
  *    readback forms) is one svo_config per context, svo_set_config; no
@@ -55,7 +55,8 @@ typedef struct svo_hit {
     uint32_t parent;     /* descriptor holding the hit leaf (NVIDIASVO.compute:177); 0xFFFFFFFF = miss */
     uint8_t  hit_idx;    /* child slot of the hit leaf = idx ^ octant_mask ^ 7 (:176) */
     uint8_t  hit_scale;  /* leaf scale, 23 - depth */
-    uint16_t flags;      /* bit0 hit, bit1 iteration cap, bit2 stack overflow, bit3 in shadow */
+    uint16_t flags;      /* bit0 hit, bit1 iteration cap, bit2 stack overflow, bit3 in shadow,
+                            bit4 invalid ray (svo_trace_rays only) */
     float    t;          /* bestHit.distance = 2048 * t_min (:163,171); +inf on miss */
     float    nx, ny, nz; /* normalize(decodeNormal(att[2*parent+1] >> 16)) (:177-182) */
 } svo_hit;
@@ -391,6 +392,72 @@ enum { SVO_PIXELS_RGBA8 = 0, SVO_PIXELS_RGB8 = 1 };
 int svo_render_progressive_async(svo_ctx *ctx, int width, int height, int stack_mode, uint32_t sample,
                                  int pixel_format, const void **frame_out);
 int svo_progressive_last(svo_ctx *ctx, const void **frame_out);
+
+/* Ray queries: trace a caller-supplied batch of world-space rays through the uploaded pool --
+ * picking, line of sight, secondary rays.  The reference has this on its CPU side only
+ * (the SVO interface's Trace(UnityEngine.Ray), Assets/Scripts/SVO/RTUtility/Interfaces.cs:6-15,
+ * driven by SVODriver.UpdateRaycast, SVODriver.cs:74-87).  No camera is involved and a query
+ * reads the node pool only: it leaves every piece of render state alone (dispatch orders, tile
+ * costs, beam starts, view-change detection, kernel-timing records, the progressive frame), so
+ * a render before and after a query gives the same bytes and takes the same path.
+ *
+ * Each ray is processed in this order:
+ *  1. classify: a ray is INVALID if any origin or direction component is non-finite, if t_max
+ *     is NaN, or if all three direction components are zero.  An invalid ray is not traced: it
+ *     gets the miss record (parent 0xFFFFFFFF, t +inf, normal 0) with flag bit 4
+ *     (SVO_HIT_INVALID_RAY), position 0, voxel key all ones, hit-mask bit 0.
+ *  2. clamp: unless SVO_QUERY_RAW_DIRECTIONS is set, every direction component with
+ *     |d| < 2^-23 becomes copysign(2^-23, d) (-0 gives -2^-23).  Deviation (documented): this
+ *     is Laine-Karras's small-direction clamp, which the reference commented out
+ *     (NVIDIASVO.compute:21-24, epsilon exp2(-s_max) at :3); without it an exactly axis-aligned
+ *     ray misses everything.  The position output uses the clamped direction.
+ *  3. trace: the walk of IntersectSVO (NVIDIASVO.compute:12-198) on that origin and direction,
+ *     in the context's pool and the given stack mode -- the primary rays' own loop; hit record,
+ *     position and voxel key are bit-identical to the CPU oracle's for the same ray.
+ * Units: `t` of the record keeps its meaning everywhere else in this header, 2048 x the
+ * SVO-space t_min; the world-space hit point is origin + (t / 64) * dir, and with a unit
+ * direction t / 64 is the world distance.  The direction is used as given, NOT normalised.
+ * t_max is a filter on the finished record, not an early exit: the ray stays a hit iff
+ * t * (1 / 64) <= t_max in f32; otherwise every output gets the plain miss record (flags 0).
+ * +inf: no limit.
+ * Outputs: every non-NULL output is fully written for all n_rays (the caller zeroes nothing),
+ * nothing is written past n_rays entries or past ceil(n_rays / 64) mask words, and the unused
+ * bits of the last mask word are 0.
+ * SVO_QUERY_ORDERED: the rays are traced in the order of a 30-bit key (3 bits octant mask, 27
+ * bits Morton code of the ray's entry point into the cube; invalid rays and rays that miss the
+ * cube last), sorted on the device, and every output is scattered to the ray's own index --
+ * placement only, the results are byte-identical to the unordered query.  Keys, indices and
+ * the sort's temporary storage are context-owned and grow-only.
+ * n_rays == 0: SVO_OK, nothing launched.  n_rays above 2^31 - 1, a NULL context, d_rays or out,
+ * an out with every pointer NULL, unknown flag bits or a bad stack mode: SVO_ERR_ARG (checked
+ * before any device is touched); no pool uploaded: SVO_ERR_STATE.  A multi-device context
+ * runs the query on devices[0].  d_rays and the outputs are device pointers on that device,
+ * d_rays 16-byte aligned.  Asynchronous on `stream` (NULL: the context's own). */
+typedef struct svo_ray {      /* 32 bytes, 16-byte aligned in device memory */
+    float origin[3];          /* world space, as CreateCameraRay's ray.origin */
+    float t_max;              /* world-space parameter limit; +inf: none */
+    float dir[3];             /* world space, used as given: NOT normalised */
+    uint32_t reserved;        /* 0 */
+} svo_ray;
+
+typedef struct svo_query_out { /* device pointers, each nullable, not all NULL */
+    svo_hit  *hits;           /* n records */
+    float    *position;       /* n float4, svo_frame.position's definition */
+    uint64_t *voxel;          /* n keys, svo_frame.voxel's definition */
+    uint64_t *hitmask;        /* ceil(n/64) words: bit i%64 of word i/64 = ray i hit */
+} svo_query_out;
+
+enum { SVO_QUERY_ORDERED = 1, SVO_QUERY_RAW_DIRECTIONS = 2 };
+enum { SVO_HIT_INVALID_RAY = 0x10 };   /* svo_hit.flags bit 4: the query's ray was invalid */
+
+int svo_trace_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n_rays, int stack_mode,
+                   uint32_t flags, const svo_query_out *out, void *stream);
+
+/* The same for HOST arrays (rays and each output nullable except rays, not all outputs NULL):
+ * staged through context-owned device buffers on the context's stream; returns when the
+ * results are on the host.  Blocking. */
+int svo_trace_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, int stack_mode,
+                        uint32_t flags, svo_hit *hits, float *position, uint64_t *voxel);
 
 /* Information about the uploaded pool. */
 int svo_get_info(svo_ctx *ctx, size_t *n_nodes, int *max_depth, int *device);

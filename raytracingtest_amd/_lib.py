@@ -36,7 +36,12 @@ EXPORTS = ("svo_create", "svo_set_buffer", "svo_set_buffer_v2", "svo_set_camera"
            "svo_assemble_frame", "svo_stage_time", "svo_render_progressive", "svo_set_band_deal",
            "svo_pack_hits", "svo_get_member_link", "svo_stage_times", "svo_render_samples",
            "svo_render_progressive_async", "svo_progressive_last", "svo_forget_stream", "svo_get_config",
-           "svo_set_config", "svo_beam_starts")
+           "svo_set_config", "svo_beam_starts", "svo_trace_rays", "svo_trace_rays_host")
+# svo_ray: one caller-supplied ray of svo_trace_rays (world space, direction used as given)
+RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")])
+assert RAY_DTYPE.itemsize == 32
+QUERY_ORDERED, QUERY_RAW_DIRECTIONS = 1, 2   # svo_trace_rays flags
+HIT_INVALID_RAY = 0x10                       # svo_hit.flags bit 4: the query's ray was invalid
 SVO_OPT_SHADOW_RAYS = 1
 SVO_OPT_KERNEL_TIMING = 2
 SVO_OPT_COUNT_BEAM = 4
@@ -85,6 +90,18 @@ class SvoFrame(ctypes.Structure):
     _fields_ = [("hits", ctypes.c_void_p), ("rgba", ctypes.c_void_p), ("rgba8", ctypes.c_void_p),
                 ("compact", ctypes.c_void_p), ("position", ctypes.c_void_p), ("voxel", ctypes.c_void_p),
                 ("rgb8", ctypes.c_void_p), ("hitmask", ctypes.c_void_p), ("layout", ctypes.c_int)]
+
+
+class SvoRay(ctypes.Structure):
+    """svo_ray, 32 bytes (RAY_DTYPE is its numpy form)."""
+    _fields_ = [("origin", ctypes.c_float * 3), ("t_max", ctypes.c_float), ("dir", ctypes.c_float * 3),
+                ("reserved", ctypes.c_uint32)]
+
+
+class SvoQueryOut(ctypes.Structure):
+    """svo_query_out: device pointers (ints) of a ray query's outputs, each nullable."""
+    _fields_ = [("hits", ctypes.c_void_p), ("position", ctypes.c_void_p), ("voxel", ctypes.c_void_p),
+                ("hitmask", ctypes.c_void_p)]
 
 
 # svo_config (include/svo_rt.h, ABI 10): the context's render policy, versioned by size
@@ -168,6 +185,8 @@ def lib():
         "svo_get_config": [vp, ctypes.POINTER(SvoConfig)],
         "svo_set_config": [vp, ctypes.POINTER(SvoConfig)],
         "svo_beam_starts": [vp, i, i, ctypes.POINTER(SvoBand), vp, vp],
+        "svo_trace_rays": [vp, vp, sz, i, ctypes.c_uint32, ctypes.POINTER(SvoQueryOut), vp],
+        "svo_trace_rays_host": [vp, vp, sz, i, ctypes.c_uint32, vp, vp, vp],
         "svo_destroy": [vp],
         "svo_last_error": [],
         "svo_abi_version": [],

@@ -13,6 +13,8 @@
 // placement) were removed (DESIGN.md 5.1 keeps their numbers).
 #include "svo_traverse.h"
 
+#include <hipcub/hipcub.hpp>   // ordered ray queries: the toolchain's device radix sort (launch_query_sort)
+
 namespace svo {
 namespace {
 
@@ -568,6 +570,27 @@ struct Record {
     unsigned long long key;   // voxel key (misses: all ones)
 };
 
+// N:165-174 for a hit ray with world-space origin org and direction dir: undo the mirroring,
+// then clamp the (x32-scaled, reference quirk) hit point into the voxel and scale it by 64.
+// Voxel key: the un-mirrored corner's mantissa bits at the leaf scale (exact: positions are dyadic).
+__device__ __forceinline__ void hit_position(const Ray &r, const float org[3], const float dir[3], Record &o) {
+    const float t_min = r.t_min * 32.0f;                  // N:163
+    const float se = r.scale_exp2;
+    float q[3] = { r.px, r.py, r.pz };
+    unsigned long long key = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (((r.octant_mask >> k) & 1) == 0) q[k] = (3.0f - se) - q[k];
+        const float hp = to_svo(org[k]) + t_min * dir[k];
+        const float lo = q[k] + 0.00000001f;
+        const float hi = (q[k] + se) - 0.00000001f;
+        const float c = fminf(fmaxf(hp, lo), hi);
+        o.pos[k] = (c - 1.5f) * 64.0f;
+        key |= (unsigned long long)((__float_as_uint(q[k]) & 0x7FFFFFu) >> r.scale) << (21 * k);
+    }
+    o.key = key;
+}
+
 // N:158-186 hit decode + R:93-127 Shade.  (x, gy): the pixel, for the hit
 // position's ray origin (recomputed, not kept live through the loop).
 __device__ __forceinline__ void record(const LaunchParams &p, const Ray &r, int x, int gy, Record &o) {
@@ -600,25 +623,9 @@ __device__ __forceinline__ void record(const LaunchParams &p, const Ray &r, int 
         shade_hit(p.cam, n, alb, o.rgb);
     }
     if (p.out.position || p.out.voxel) {
-        // N:165-174: undo the mirroring, then clamp the (x32-scaled, reference quirk)
-        // hit point into the voxel and scale it by 64.  Voxel key: the un-mirrored
-        // corner's mantissa bits at the leaf scale (exact: positions are dyadic).
         float org[3], dir[3];
         camera_ray(p.cam, p.width, p.height, x, gy, org, dir);
-        const float se = r.scale_exp2;
-        float q[3] = { r.px, r.py, r.pz };
-        unsigned long long key = 0;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (((r.octant_mask >> k) & 1) == 0) q[k] = (3.0f - se) - q[k];
-            const float hp = to_svo(org[k]) + t_min * dir[k];
-            const float lo = q[k] + 0.00000001f;
-            const float hi = (q[k] + se) - 0.00000001f;
-            const float c = fminf(fmaxf(hp, lo), hi);
-            o.pos[k] = (c - 1.5f) * 64.0f;
-            key |= (unsigned long long)((__float_as_uint(q[k]) & 0x7FFFFFu) >> r.scale) << (21 * k);
-        }
-        o.key = key;
+        hit_position(r, org, dir, o);
     }
 }
 
@@ -1526,6 +1533,131 @@ __global__ __launch_bounds__(TILE) void shadow_list_kernel(LaunchParams p, const
     }
 }
 
+// -------------------------------------------------------------- ray queries
+// svo_trace_rays (svo_rt.h): a flat list of caller-supplied world-space rays, traced with the
+// primary rays' own loop.  The front end of a ray is classify, then clamp:
+//   * invalid (not traced): a non-finite origin or direction component, a NaN t_max, or a zero
+//     direction;
+//   * unless QUERY_RAW, a direction component below 2^-23 in magnitude becomes copysign(2^-23, d):
+//     Laine-Karras's small-direction clamp, which the reference commented out (N:21-24, epsilon
+//     exp2(-s_max) at N:3) -- with the reference's arithmetic an exactly axis-aligned ray has an
+//     infinite coefficient, NaN corner times, and misses everything.  A documented deviation.
+__device__ __forceinline__ bool finite_f32(float v) { return (__float_as_uint(v) & 0x7F800000u) != 0x7F800000u; }
+
+// Ray i of the list as it is traced; false: invalid.  Two 16-byte loads.
+__device__ __forceinline__ bool query_ray(const QueryArgs &q, uint32_t i, float org[3], float dir[3], float &t_max) {
+    const float4 *src = reinterpret_cast<const float4 *>(q.rays) + 2 * (size_t)i;
+    const float4 a = src[0], b = src[1];
+    org[0] = a.x; org[1] = a.y; org[2] = a.z; t_max = a.w;
+    dir[0] = b.x; dir[1] = b.y; dir[2] = b.z;
+    bool ok = !(t_max != t_max) && !(dir[0] == 0.0f && dir[1] == 0.0f && dir[2] == 0.0f);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) ok = ok && finite_f32(org[k]) && finite_f32(dir[k]);
+    if (!(q.flags & QUERY_RAW)) {
+        constexpr float EPS = 0x1p-23f;
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (fabsf(dir[k]) < EPS) dir[k] = __builtin_copysignf(EPS, dir[k]);
+    }
+    return ok;
+}
+
+__device__ __forceinline__ void miss_record(Record &o, uint32_t flags) {
+    o.w[0] = 0xFFFFFFFFu;
+    o.w[1] = flags << 16;
+    o.w[2] = 0x7F800000u;
+    o.w[3] = 0u; o.w[4] = 0u; o.w[5] = 0u;
+    o.rgb[0] = o.rgb[1] = o.rgb[2] = 0.0f;
+    o.pos[0] = o.pos[1] = o.pos[2] = 0.0f;
+    o.key = ~0ull;
+}
+
+// One wave64 traces 64 consecutive list entries (shadow_list_kernel's shape: the same [slot][lane]
+// LDS stack, the same loop; all lanes of a wave start together, so the wave-uniform trip count is
+// each tracing lane's own iteration count and the cap is the oracle's).  Invalid rays and lanes
+// past the list leave before the loop with their outputs written.  The hit position is rebuilt from
+// the ray's own (clamped) origin and direction.  t_max filters the finished record: a hit stays one
+// iff t * (1 / 64) <= t_max -- no lane retires early on it (the loop's t_min is not provably
+// monotone in f32 across ADVANCE, so an early exit could differ from this definition).
+template <int MODE, bool GUARD, bool FA>
+__global__ __launch_bounds__(TILE) void query_rays_kernel(LaunchParams p, QueryArgs q) {
+    extern __shared__ uint2 stk_base[];
+    const int lane = (int)threadIdx.x;
+    const uint32_t k = blockIdx.x * TILE + (uint32_t)lane;
+    const bool in = k < q.n;
+    const uint32_t i = (in && q.index) ? q.index[k] : k;
+    float org[3] = {0.0f, 0.0f, 0.0f}, dir[3] = {0.0f, 0.0f, 0.0f}, t_lim = 0.0f;
+    const bool valid = in && query_ray(q, i, org, dir, t_lim);
+    const bool any_valid = LM_OF(valid) != 0;   // whole wave, before any lane leaves
+    Record o;
+    if (!valid) {
+        if (in) {
+            miss_record(o, HIT_INVALID_RAY);
+            store_outputs(q.out, i, o);
+        }
+        // lane 0 is always inside the list (the grid is ceil(n / 64) waves)
+        if (!any_valid && lane == 0 && q.out.hitmask && !q.index) q.out.hitmask[blockIdx.x] = 0ull;
+        return;
+    }
+    Ray r;
+    setup_ray(org, dir, r);
+    uint2 *stk = stk_base + lane;
+    FRay f;
+    to_fray(r, f);
+    trace_lean<MODE, GUARD, false, FA>(p, f, stk);
+    from_fray(f, r);
+    record(p, r, 0, 0, o);   // p.out is empty: the hit words only (position and key below)
+    bool hit = r.scale < S_MAX;
+    if (hit && !(__uint_as_float(o.w[2]) * (1.0f / 64.0f) <= t_lim)) {
+        miss_record(o, 0u);
+        hit = false;
+    }
+    if (hit && (q.out.position || q.out.voxel)) hit_position(r, org, dir, o);
+    store_outputs(q.out, i, o);
+    if (q.out.hitmask) {
+        if (q.index) {   // ordered: the wave's lanes belong to 64 different words (zeroed by launch_query)
+            if (hit) atomicOr(q.out.hitmask + (i >> 6), 1ull << (i & 63u));
+        } else {         // the wave's ballot; lanes that left above are outside it: bit 0
+            const lmask m = LM_OF(hit), live = LM_OF(true);
+            if (lane == __builtin_ctzll(live)) q.out.hitmask[blockIdx.x] = m;
+        }
+    }
+}
+
+// Ordered mode's placement key of every ray: octant mask << 27 | the 27-bit Morton code (9 bits
+// per axis) of the point where the ray enters the cube; all ones for rays that are invalid or miss
+// the cube, so they sort last.  Placement only: any key gives the same results.
+__device__ __forceinline__ uint32_t spread3(uint32_t v) {   // 9 bits -> every third bit
+    v = (v | (v << 16)) & 0x030000FFu;
+    v = (v | (v << 8)) & 0x0300F00Fu;
+    v = (v | (v << 4)) & 0x030C30C3u;
+    v = (v | (v << 2)) & 0x09249249u;
+    return v;
+}
+
+__global__ __launch_bounds__(256) void query_keys_kernel(QueryArgs q, uint32_t *__restrict__ keys,
+                                                         uint32_t *__restrict__ index) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= q.n) return;
+    float org[3], dir[3], t_lim;
+    uint32_t key = (1u << QUERY_KEY_BITS) - 1u;
+    if (query_ray(q, i, org, dir, t_lim)) {
+        Ray r;
+        setup_ray(org, dir, r);
+        if (r.t_min <= r.t_max) {   // the cube's entry before its exit (false for NaN)
+            uint32_t g[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const float e = (to_svo(org[k]) + r.t_min * dir[k] - 1.0f) * 512.0f;
+                g[k] = (uint32_t)fminf(fmaxf(e, 0.0f), 511.0f);   // NaN -> 0
+            }
+            key = ((uint32_t)r.octant_mask << 27) | spread3(g[0]) | (spread3(g[1]) << 1) | (spread3(g[2]) << 2);
+        }
+    }
+    keys[i] = key;
+    index[i] = i;
+}
+
 // ---------------------------------------------------------- frame assembly
 // svo_assemble_frame: one thread per pixel of the frame (one row per grid y).
 // Row y belongs to band b = y / band_rows and, round-robin, to part m = b % n_parts
@@ -1679,6 +1811,50 @@ static hipError_t launch_variant(const LaunchParams &p, hipStream_t stream) {
     else
         hipLaunchKernelGGL((render_tile_kernel<MODE, false>), grid, block, lds, stream, p, bx);
     return hipGetLastError();
+}
+
+// ---------------------------------------------------------- ray queries
+template <int MODE>
+static hipError_t launch_query_mode(const LaunchParams &p, const QueryArgs &q, hipStream_t stream) {
+    const size_t lds = (size_t)p.slots * TILE * sizeof(uint2) + lds_pad();
+    const dim3 grid((q.n + (uint32_t)TILE - 1u) / (uint32_t)TILE), block(TILE);
+    if (p.guard)
+        hipLaunchKernelGGL((query_rays_kernel<MODE, true, false>), grid, block, lds, stream, p, q);
+    else if (p.fetch_all)
+        hipLaunchKernelGGL((query_rays_kernel<MODE, false, true>), grid, block, lds, stream, p, q);
+    else
+        hipLaunchKernelGGL((query_rays_kernel<MODE, false, false>), grid, block, lds, stream, p, q);
+    return hipGetLastError();
+}
+
+hipError_t launch_query(const LaunchParams &p, const QueryArgs &q, int stack_mode, hipStream_t stream) {
+    if (q.n == 0) return hipSuccess;
+    if (q.index && q.out.hitmask) {   // ordered: hit lanes or their bits in
+        const hipError_t e = hipMemsetAsync(q.out.hitmask, 0, (((size_t)q.n + 63) / 64) * sizeof(unsigned long long), stream);
+        if (e != hipSuccess) return e;
+    }
+    return stack_mode == 0 ? launch_query_mode<0>(p, q, stream) : launch_query_mode<1>(p, q, stream);
+}
+
+hipError_t launch_query_keys(const QueryArgs &q, uint32_t *keys, uint32_t *index, hipStream_t stream) {
+    if (q.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(query_keys_kernel, dim3((q.n + 255u) / 256u), dim3(256), 0, stream, q, keys, index);
+    return hipGetLastError();
+}
+
+size_t query_sort_bytes(uint32_t n) {
+    size_t bytes = 0;
+    const uint32_t *k = nullptr;
+    uint32_t *ko = nullptr;
+    if (hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, k, ko, k, ko, (int)n, 0, (int)QUERY_KEY_BITS) != hipSuccess)
+        return 0;
+    return std::max(bytes, (size_t)16);
+}
+
+hipError_t launch_query_sort(const uint32_t *keys, uint32_t *keys_out, const uint32_t *index, uint32_t *index_out,
+                             uint32_t n, void *temp, size_t temp_bytes, hipStream_t stream) {
+    return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys, keys_out, index, index_out, (int)n, 0,
+                                              (int)QUERY_KEY_BITS, stream);
 }
 
 // ---------------------------------------------------------- tile order

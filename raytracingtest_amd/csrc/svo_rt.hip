@@ -372,6 +372,19 @@ struct svo_ctx {
     hipStream_t scratch_stream = nullptr;
     bool scratch_valid = false;
     hipEvent_t switch_event = nullptr;
+    // Ray queries (svo_trace_rays): render state is never touched; the only state is scratch,
+    // grow-only, handed from stream to stream like the host-path scratch above (an event recorded
+    // on the previous user's stream at the switch).  Ordered mode: keys and indices (in, out) and
+    // the radix sort's temporary storage; the host path: the staged rays and outputs.
+    uint32_t *q_keys = nullptr;          // 4 x q_cap words: keys, sorted keys, indices, sorted indices
+    size_t q_cap = 0;
+    void *q_temp = nullptr;
+    size_t q_temp_cap = 0;
+    void *q_host = nullptr;              // rays, hits, positions, voxel keys of q_host_cap rays
+    size_t q_host_cap = 0;
+    hipStream_t q_stream = nullptr;
+    bool q_valid = false;
+    hipEvent_t q_event = nullptr;
     // multi-device context (svo_create_multi); empty for a single-device one
     std::vector<svo_ctx *> members;
     std::vector<Peer> peers;
@@ -1784,6 +1797,10 @@ int destroy_single(svo_ctx *ctx) {
         for (auto &ev : v) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     for (auto &ev : ctx->timing_free) { hipEventDestroy(ev.first); hipEventDestroy(ev.second); }
     if (ctx->switch_event) hipEventDestroy(ctx->switch_event);
+    if (ctx->q_keys) hipFree(ctx->q_keys);
+    if (ctx->q_temp) hipFree(ctx->q_temp);
+    if (ctx->q_host) hipFree(ctx->q_host);
+    if (ctx->q_event) hipEventDestroy(ctx->q_event);
     if (ctx->d_wave_log) hipFree(ctx->d_wave_log);
     for (DevBoxes &db : ctx->dev_boxes)
         if (db.d) hipFree(db.d);
@@ -1925,9 +1942,150 @@ int apply_config(svo_ctx *c, const svo_config &k) {
     return SVO_OK;
 }
 
+// ------------------------------------------------------------------ ray queries
+// Make stream s wait for the query-scratch work the previous user enqueued on another stream
+// (order_scratch's rule, for the query's own scratch).
+int order_query_scratch(svo_ctx *c, hipStream_t s) {
+    if (c->q_valid && c->q_stream != s) {
+        if (!c->q_event) HIP_TRY(hipEventCreateWithFlags(&c->q_event, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->q_event, c->q_stream));
+        HIP_TRY(hipStreamWaitEvent(s, c->q_event, 0));
+    }
+    c->q_stream = s;
+    c->q_valid = true;
+    return SVO_OK;
+}
+
+// Grow-only device scratch: *buf holds at least `need` bytes afterwards.
+int grow_query_scratch(void **buf, size_t *cap, size_t need) {
+    if (need <= *cap) return SVO_OK;
+    HIP_TRY(hipDeviceSynchronize());   // an earlier asynchronous query may still use the old scratch
+    if (*buf) hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    HIP_TRY(hipMalloc(buf, need));
+    *cap = need;
+    return SVO_OK;
+}
+
+constexpr size_t MAX_QUERY_RAYS = ((size_t)1 << 31) - 1;
+
+// The argument checks of both entry points that need no device and no context state.
+int check_query_args(size_t n_rays, int stack_mode, uint32_t flags) {
+    if (flags & ~(uint32_t)(SVO_QUERY_ORDERED | SVO_QUERY_RAW_DIRECTIONS)) return fail(SVO_ERR_ARG, "unknown query flag bits");
+    if (stack_mode != SVO_STACK_HLSL && stack_mode != SVO_STACK_EXACT) return fail(SVO_ERR_ARG, "unknown stack mode");
+    if (n_rays > MAX_QUERY_RAYS) return fail(SVO_ERR_ARG, "more than 2^31 - 1 rays in one query");
+    return SVO_OK;
+}
+
+// One query on context c (single-device), its device selected: arguments checked by the caller.
+int query_device(svo_ctx *c, const svo_ray *d_rays, size_t n_rays, int stack_mode, uint32_t flags,
+                 const svo_query_out &out, hipStream_t s) {
+    if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
+    if ((uintptr_t)d_rays & 15u) return fail(SVO_ERR_ARG, "d_rays must be 16-byte aligned");
+    svo::LaunchParams p;
+    std::memset(&p, 0, sizeof p);
+    p.nodes = c->d_nodes;
+    p.att = c->d_att;
+    p.n_nodes = (uint32_t)std::min<size_t>(c->n_nodes, 0xFFFFFFFFu);
+    // loop form: exactly the render launch's choice for this pool (launch)
+    p.slots = std::max(c->depth - 1, 1);
+    p.guard = !c->depth_exact || (stack_mode == 0 && c->n_nodes > ((size_t)1 << 24)) || c->n_nodes >= ((size_t)1 << 29);
+    p.fetch_all = c->fetch_all >= 0 ? c->fetch_all : (c->n_nodes < ((size_t)1 << 24) ? 1 : 0);
+    svo::QueryArgs q;
+    std::memset(&q, 0, sizeof q);
+    q.rays = reinterpret_cast<const svo::QueryRay *>(d_rays);
+    q.n = (uint32_t)n_rays;
+    q.flags = (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u;
+    q.out.hits = reinterpret_cast<svo::Hit *>(out.hits);
+    q.out.position = reinterpret_cast<float4 *>(out.position);
+    q.out.voxel = reinterpret_cast<unsigned long long *>(out.voxel);
+    q.out.hitmask = reinterpret_cast<unsigned long long *>(out.hitmask);
+    if (flags & SVO_QUERY_ORDERED) {
+        const size_t temp = svo::query_sort_bytes(q.n);
+        if (temp == 0) return fail(SVO_ERR_HIP, "radix sort: temporary storage query failed");
+        int rc = grow_query_scratch(reinterpret_cast<void **>(&c->q_keys), &c->q_cap, 4 * n_rays * sizeof(uint32_t));
+        if (rc) return rc;
+        rc = grow_query_scratch(&c->q_temp, &c->q_temp_cap, temp);
+        if (rc) return rc;
+        rc = order_query_scratch(c, s);
+        if (rc) return rc;
+        uint32_t *keys = c->q_keys, *keys_out = keys + n_rays, *index = keys + 2 * n_rays, *index_out = keys + 3 * n_rays;
+        hipError_t e = svo::launch_query_keys(q, keys, index, s);
+        if (e == hipSuccess) e = svo::launch_query_sort(keys, keys_out, index, index_out, q.n, c->q_temp, temp, s);
+        if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("query order: ") + hipGetErrorString(e));
+        q.index = index_out;
+    }
+    const hipError_t e = svo::launch_query(p, q, stack_mode, s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("query launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int svo_trace_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n_rays, int stack_mode, uint32_t flags,
+                   const svo_query_out *out, void *stream) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!d_rays) return fail(SVO_ERR_ARG, "null ray list");
+    if (!out) return fail(SVO_ERR_ARG, "null svo_query_out");
+    if (!out->hits && !out->position && !out->voxel && !out->hitmask) return fail(SVO_ERR_ARG, "every query output is null");
+    int rc = check_query_args(n_rays, stack_mode, flags);
+    if (rc) return rc;
+    if (n_rays == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
+        HIP_TRY(hipSetDevice(c->device));
+        return query_device(c, d_rays, n_rays, stack_mode, flags, *out, stream ? (hipStream_t)stream : c->stream);
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_trace_rays: ") + e.what());
+    }
+}
+
+int svo_trace_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, int stack_mode, uint32_t flags,
+                        svo_hit *hits, float *position, uint64_t *voxel) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!rays) return fail(SVO_ERR_ARG, "null ray list");
+    if (!hits && !position && !voxel) return fail(SVO_ERR_ARG, "every query output is null");
+    int rc = check_query_args(n_rays, stack_mode, flags);
+    if (rc) return rc;
+    if (n_rays == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
+        HIP_TRY(hipSetDevice(c->device));
+        // staged layout: rays (32 B), positions (16 B), hit records (24 B), voxel keys (8 B) per ray --
+        // every part 16-byte aligned for any n (the records' part starts at a multiple of 48 n)
+        const size_t n = n_rays, off_pos = 32 * n, off_hits = 48 * n, off_vox = (72 * n + 15) & ~(size_t)15;
+        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, off_vox + 8 * n);
+        if (rc) return rc;
+        rc = order_query_scratch(c, c->stream);
+        if (rc) return rc;
+        char *base = static_cast<char *>(c->q_host);
+        // every exit waits for the stream: no copy may still read or write the caller's arrays once
+        // this call has returned (an error included)
+        struct Drain {
+            hipStream_t s;
+            ~Drain() { hipStreamSynchronize(s); }
+        } drain{c->stream};
+        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
+        svo_query_out out{};
+        out.hits = hits ? reinterpret_cast<svo_hit *>(base + off_hits) : nullptr;
+        out.position = position ? reinterpret_cast<float *>(base + off_pos) : nullptr;
+        out.voxel = voxel ? reinterpret_cast<uint64_t *>(base + off_vox) : nullptr;
+        rc = query_device(c, reinterpret_cast<const svo_ray *>(base), n, stack_mode, flags, out, c->stream);
+        if (rc) return rc;
+        if (hits) HIP_TRY(hipMemcpyAsync(hits, out.hits, 24 * n, hipMemcpyDeviceToHost, c->stream));
+        if (position) HIP_TRY(hipMemcpyAsync(position, out.position, 16 * n, hipMemcpyDeviceToHost, c->stream));
+        if (voxel) HIP_TRY(hipMemcpyAsync(voxel, out.voxel, 8 * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SVO_OK;
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_trace_rays_host: ") + e.what());
+    }
+}
 
 int svo_get_config(svo_ctx *ctx, svo_config *cfg) {
     if (!cfg) return fail(SVO_ERR_ARG, "cfg is null");
@@ -2643,10 +2801,14 @@ int svo_forget_stream(svo_ctx *ctx, void *stream) {
     }
     HIP_TRY(hipSetDevice(ctx->device));
     hipStream_t s = static_cast<hipStream_t>(stream);
-    bool known = ctx->scratch_valid && ctx->scratch_stream == s;
+    bool known = (ctx->scratch_valid && ctx->scratch_stream == s) || (ctx->q_valid && ctx->q_stream == s);
     for (Sched &q : ctx->sched) known = known || (q.used && q.stream == s);
     if (!known) return SVO_OK;
     HIP_TRY(hipStreamSynchronize(s));
+    if (ctx->q_valid && ctx->q_stream == s) {   // the query scratch: nothing of s is pending on it now
+        ctx->q_valid = false;
+        ctx->q_stream = nullptr;
+    }
     for (Sched &q : ctx->sched) {
         if (!q.used || q.stream != s) continue;
         // the set's buffers stay allocated for the next stream; only the stream is forgotten
@@ -2686,6 +2848,8 @@ int svo_synchronize(svo_ctx *ctx) {
     for (Sched &q : ctx->sched) q.idle = true;
     ctx->scratch_valid = false;
     ctx->scratch_stream = nullptr;
+    ctx->q_valid = false;
+    ctx->q_stream = nullptr;
     return SVO_OK;
 }
 

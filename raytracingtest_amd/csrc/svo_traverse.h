@@ -247,4 +247,36 @@ hipError_t launch_pack_rgba8(const float4 *src, uint32_t *dst, size_t n_px, int 
 hipError_t launch_render(const LaunchParams &p, int stack_mode, hipStream_t stream, hipEvent_t primary_start = nullptr,
                          hipEvent_t primary_end = nullptr);
 
+// Ray queries (svo_trace_rays; svo_kernel.hip query_rays_kernel): one wave64 traces 64
+// consecutive entries of a flat list of world-space rays with the primary rays' lean loop.
+struct QueryRay {             // == svo_ray
+    float org[3];
+    float t_max;
+    float dir[3];
+    uint32_t reserved;
+};
+static_assert(sizeof(QueryRay) == 32, "ray record layout");
+constexpr uint32_t QUERY_RAW = 2u;              // SVO_QUERY_RAW_DIRECTIONS: no small-direction clamp
+constexpr uint32_t HIT_INVALID_RAY = 0x10u;     // svo_hit.flags of an invalid ray's miss record
+constexpr uint32_t QUERY_KEY_BITS = 30;         // ordered mode's key: octant mask << 27 | 27-bit Morton code
+struct QueryArgs {
+    const QueryRay *rays;     // 16-byte aligned
+    uint32_t n;               // rays (<= 2^31)
+    uint32_t flags;           // QUERY_RAW
+    // ordered mode: list entry k traces ray index[k] (a permutation of 0 .. n - 1) and every output
+    // goes to that ray's own index; the mask is then or-ed in bit by bit (zeroed by launch_query).
+    // null: entry k = ray k, mask word = the wave's ballot
+    const uint32_t *index;
+    Outputs out;              // hits, position, voxel, hitmask (ceil(n / 64) words); the rest null
+};
+// p: nodes, att, n_nodes, slots, guard, fetch_all as launch_render's; everything else zero.
+hipError_t launch_query(const LaunchParams &p, const QueryArgs &q, int stack_mode, hipStream_t stream);
+// Ordered mode: keys[i] = the 30-bit placement key of ray i (all ones: invalid, or misses the cube),
+// index[i] = i; then (keys, index) sorted by key into (keys_out, index_out) with the toolchain's
+// device radix sort (temp: query_sort_bytes(n) bytes).
+hipError_t launch_query_keys(const QueryArgs &q, uint32_t *keys, uint32_t *index, hipStream_t stream);
+size_t query_sort_bytes(uint32_t n);
+hipError_t launch_query_sort(const uint32_t *keys, uint32_t *keys_out, const uint32_t *index, uint32_t *index_out,
+                             uint32_t n, void *temp, size_t temp_bytes, hipStream_t stream);
+
 }  // namespace svo

@@ -19,6 +19,8 @@ Beyond the reference (one GPU, one Dispatch):
                                  compact records, hit position, voxel key)
   assemble_frame(...)            rebuild a frame from band parts (the display side
                                  of the one-process-per-GPU split)
+  TraceRays(origins, dirs)       caller-supplied ray batches (the reference's CPU-side
+  trace_rays_device(...)         SVO.Trace(Ray), Interfaces.cs:6-15) on the GPU
 Errors surface as SvoError (the C-ABI status + svo_last_error text) instead of
 Unity's silent shader failures.  There is no CPU fallback.
 """
@@ -338,6 +340,50 @@ class RaytracingMaster:
         band = band if band is not None else (self.band_rows, 0, 1)
         b = ctypes.byref(band if isinstance(band, _lib.SvoBand) else make_band(band))
         check(_lib.lib().svo_pack_hits(self._ctx, width, height, b, rgb8, part, stream), "svo_pack_hits")
+
+    # ------------------------------------------------------------ ray queries
+    @staticmethod
+    def _query_flags(ordered, raw):
+        return (_lib.QUERY_ORDERED if ordered else 0) | (_lib.QUERY_RAW_DIRECTIONS if raw else 0)
+
+    def TraceRays(self, origins, dirs=None, t_max=None, stack_mode=STACK_HLSL, ordered=False, raw=False,
+                  want_position=False, want_voxel=False):
+        """Trace a batch of world-space rays through the SVO (svo_trace_rays_host; the reference's
+        CPU-side SVO.Trace(Ray), Interfaces.cs:6-15): picking, line of sight, secondary rays.
+        origins, dirs: [n, 3] (a direction is used as given, not normalised), or origins an
+        array of svo_ray records (query.make_rays) and dirs None.  t_max: scalar or [n], the
+        world-space parameter limit (None: no limit).  Each ray is classified and its small
+        direction components clamped before it is traced (query.sanitize_rays; raw=True:
+        no clamp).  ordered=True traces the rays sorted by octant and entry point: the same
+        results (measured slower with its sort included).  Blocking.  Returns the hit records
+        (HIT_DTYPE [n]; t / 64 = the ray parameter of the hit; flag 0x10: invalid ray), or
+        (hits, position [n, 4] or None, voxel keys [n] or None) when either is asked for."""
+        from .query import make_rays
+        if dirs is None:
+            rays = np.ascontiguousarray(origins, _lib.RAY_DTYPE).reshape(-1)
+            if t_max is not None:
+                rays = rays.copy()
+                rays["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), (len(rays),))
+        else:
+            rays = make_rays(origins, dirs, np.inf if t_max is None else t_max)
+        n = len(rays)
+        hits = np.zeros(n, HIT_DTYPE)
+        pos = np.zeros((n, 4), np.float32) if want_position else None
+        vox = np.zeros(n, np.uint64) if want_voxel else None
+        check(_lib.lib().svo_trace_rays_host(self._ctx, rays.ctypes.data, n, stack_mode, self._query_flags(ordered, raw),
+                                             hits.ctypes.data, None if pos is None else pos.ctypes.data,
+                                             None if vox is None else vox.ctypes.data), "svo_trace_rays_host")
+        return (hits, pos, vox) if (want_position or want_voxel) else hits
+
+    def trace_rays_device(self, rays_ptr, n, hits=None, position=None, voxel=None, hitmask=None,
+                          stack_mode=STACK_HLSL, ordered=False, raw=False, stream=None):
+        """Asynchronous ray query on device buffers (svo_trace_rays): rays_ptr = n svo_ray
+        records (32 bytes each, 16-byte aligned); hits (n x 24 bytes), position (n float4),
+        voxel (n uint64) and hitmask (ceil(n / 64) uint64) are raw device pointers, each
+        nullable, and are fully written."""
+        out = _lib.SvoQueryOut(hits, position, voxel, hitmask)
+        check(_lib.lib().svo_trace_rays(self._ctx, rays_ptr, int(n), stack_mode, self._query_flags(ordered, raw),
+                                        ctypes.byref(out), stream), "svo_trace_rays")
 
     def beam_starts_device(self, width, height, starts_ptr, band=None, stream=None):
         """svo_beam_starts: every primary ray's beam start (SVO-space t, -inf: the cube entry) into a

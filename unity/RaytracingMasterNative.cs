@@ -5,6 +5,7 @@
 using System;
 using System.Runtime.InteropServices;
 using UnityEngine;
+using static SvoNative;   // SvoHit in the MonoBehaviour's Raycast signatures
 
 public static class SvoNative {
     const string Lib = "svo_rt";        // libsvo_rt.so in Assets/Plugins/x86_64
@@ -60,6 +61,25 @@ public static class SvoNative {
     }
     [DllImport(Lib)] public static extern int svo_get_config(IntPtr ctx, ref SvoConfig cfg);
     [DllImport(Lib)] public static extern int svo_set_config(IntPtr ctx, ref SvoConfig cfg);
+
+    // Ray queries (svo_trace_rays, include/svo_rt.h): the GPU counterpart of the reference's CPU-side
+    // SVO.Trace(UnityEngine.Ray) (Interfaces.cs:6-15).  svo_ray: 32 bytes, the header's field order.
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoRay {
+        public float originX, originY, originZ;   // world space
+        public float tMax;                        // ray-parameter limit (+inf: none)
+        public float dirX, dirY, dirZ;            // used as given, not normalised
+        public uint reserved;                     // 0
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoQueryOut { public IntPtr hits, position, voxel, hitmask; }   // device pointers
+    public const uint QueryOrdered = 1, QueryRawDirections = 2;
+    public const ushort HitInvalidRay = 0x10;     // SvoHit.flags bit 4
+    [DllImport(Lib)] public static extern int svo_trace_rays(IntPtr ctx, IntPtr dRays, UIntPtr nRays, int stackMode,
+                                                             uint flags, ref SvoQueryOut output, IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_trace_rays_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr nRays,
+                                                                  int stackMode, uint flags, [Out] SvoHit[] hits,
+                                                                  [Out] float[] position, [Out] ulong[] voxel);
 
     [StructLayout(LayoutKind.Sequential)]
     public struct SvobResult {   // == svob_result
@@ -132,6 +152,43 @@ public class RaytracingMasterNative : MonoBehaviour {
             transform.hasChanged = false;
         }
         if (Input.GetKeyDown(KeyCode.R)) SetSVOBuffer();
+    }
+
+    // SVODriver.UpdateRaycast's query (SVODriver.cs:74-87) on the GPU: the first voxel along the ray within
+    // maxDistance (direction normalised here, so hit.t / 64 is the world distance).  Exactly axis-aligned
+    // directions work: the plugin restores the small-direction clamp the reference commented out.
+    public bool Raycast(Vector3 origin, Vector3 direction, float maxDistance, out SvoHit hit, out Vector3 point) {
+        var rays = new[] { new Ray(origin, direction) };
+        SvoHit[] hits;
+        Vector3[] points;
+        Raycast(rays, maxDistance, out hits, out points);
+        hit = hits[0];
+        point = points[0];
+        return (hit.flags & 1) != 0;
+    }
+
+    // Batch overload: one svo_trace_rays_host call for all rays; returns the number of hits.  ordered: trace in
+    // the order of the rays' octant and entry point (the same results; measured slower, DESIGN.md 3.2b).
+    public int Raycast(Ray[] rays, float maxDistance, out SvoHit[] hits, out Vector3[] points, bool ordered = false) {
+        var list = new SvoNative.SvoRay[rays.Length];
+        for (int i = 0; i < rays.Length; i++) {
+            Vector3 o = rays[i].origin, d = rays[i].direction;   // UnityEngine.Ray keeps a unit direction
+            list[i] = new SvoNative.SvoRay { originX = o.x, originY = o.y, originZ = o.z, tMax = maxDistance,
+                                             dirX = d.x, dirY = d.y, dirZ = d.z, reserved = 0 };
+        }
+        hits = new SvoHit[rays.Length];
+        points = new Vector3[rays.Length];
+        if (rays.Length == 0) return 0;
+        SvoNative.Check(SvoNative.svo_trace_rays_host(_ctx, list, (UIntPtr)rays.Length, _stackMode,
+                                                      ordered ? SvoNative.QueryOrdered : 0u, hits, null, null),
+                        "svo_trace_rays_host");
+        int n = 0;
+        for (int i = 0; i < rays.Length; i++) {
+            if ((hits[i].flags & 1) == 0) continue;
+            points[i] = rays[i].GetPoint(hits[i].t / 64.0f);   // world hit point = origin + (t / 64) dir
+            n++;
+        }
+        return n;
     }
 
     // RaytracingMaster.cs:111-116
