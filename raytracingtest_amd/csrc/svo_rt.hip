@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "svo_rt.h"
+#include "svo_sched.h"
 #include "svo_traverse.h"
 
 namespace {
@@ -82,19 +83,7 @@ struct DevBoxes {
 
 enum { STAGE_KERNEL = 0, STAGE_ASSEMBLE = 1, N_STAGES = 2 };
 
-// The tile-order cache key: the exact geometry (and deal) an order was built for.
-struct Geo {
-    int width = -1, local_rows = -1, rows = -1, rank = -1, count = -1, xcd = -1, n_tiles = -1;
-    int seg = 0;    // the order's seg_cap (segmented heavy tiles, svo_kernel.hip render_seg_kernel) ...
-    int kpack = 0;  // ... and the K of each cost class (launch_order_strips' seg_kpack)
-    uint64_t deal = 0;
-    bool operator==(const Geo &o) const {
-        return width == o.width && local_rows == o.local_rows && rows == o.rows && rank == o.rank &&
-               count == o.count && xcd == o.xcd && n_tiles == o.n_tiles && seg == o.seg && kpack == o.kpack &&
-               deal == o.deal;
-    }
-    bool operator!=(const Geo &o) const { return !(*this == o); }
-};
+using svo_sched::Geo;   // the tile-order cache key (svo_sched.h)
 
 // Cost-ordered dispatch state of the renders on one stream: every launch records each
 // 8x8 tile's trip count; the order kernel, enqueued right behind it, turns them into
@@ -456,6 +445,19 @@ void free_sched(Sched &q) {
     q.cap = 0;
     q.order_cap = 0;
     reset_builds(q);
+}
+
+// The grow-only device buffer: replace *buf by one of `bytes` bytes; *cap, in the owner's own unit,
+// is 0 while there is none and new_cap afterwards.  The caller has waited for whatever may still
+// use the old buffer (its stream, or the device).
+template <class T>
+int regrow(T **buf, size_t *cap, size_t new_cap, size_t bytes) {
+    if (*buf) hipFree(*buf);
+    *buf = nullptr;
+    *cap = 0;
+    HIP_TRY(hipMalloc(buf, bytes));
+    *cap = new_cap;
+    return SVO_OK;
 }
 
 // The scheduling state of stream s: its own set, or a free one, or the least recently
@@ -986,22 +988,30 @@ bool beam_camera(const svo::Camera &c, int width, int height, svo::BeamParams *b
     return true;
 }
 
-int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *band, svo::Outputs out,
-           hipStream_t stream, const SampleArgs *sa = nullptr) {
-    if (!ctx) return fail(SVO_ERR_ARG, "null context");
-    if (width <= 0 || height <= 0) return fail(SVO_ERR_ARG, "width/height must be positive");
-    if ((size_t)width * (size_t)height > ((size_t)1 << 31)) return fail(SVO_ERR_ARG, "frame larger than 2^31 pixels");
-    if (stack_mode != SVO_STACK_HLSL && stack_mode != SVO_STACK_EXACT)
-        return fail(SVO_ERR_ARG, "unknown stack mode");
-    if (ctx->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
-    if (!ctx->cam_set) return fail(SVO_ERR_STATE, "camera not set (svo_set_camera)");
+// What the phases of one launch (below, in launch's order) share.
+struct LaunchPlan {
     Deal b;
-    int rc = check_band(band, height, &b);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(ctx->device));
-    svo::LaunchParams p;
+    int stack_mode = 0;
+    hipStream_t s = nullptr;
+    Sched *q = nullptr;   // the stream's scheduling state (null: strip order, or an instrumented launch)
+    Geo key;              // the geometry (seg 0): the key of the costs and of the loop-form decision
+    Geo okey;             // the order's key: key + the seg_cap and class table its order was built with
+    int seg_cap = 0, n_tiles = 0;
+    int mode_now = 0;     // the render mode the costs are keyed on: shadows | stack_mode << 2
+    int used_kpack = 0;   // the class layout of the order this launch dispatches in
+    bool instr = false;   // instrumented: svo_count_fetches / svo_beam_starts
+    bool jittered = false;       // per-launch pixel offsets: the tiles' costs drift without a new view
+    bool latency_bound = false;
+    bool beam_planned = false;   // this launch's primary rays get beam starts (less the per-launch camera checks)
+    size_t n_wave = 0;    // wave-log records: one per workgroup
+};
+
+// The launch parameters every form starts from.
+void base_params(const svo_ctx *ctx, const LaunchPlan &L, int width, int height, const svo::Outputs &out,
+                 svo::LaunchParams &p) {
+    const Deal &b = L.b;
+    const int stack_mode = L.stack_mode;
     std::memset(&p, 0, sizeof p);
-    bool jittered = false;   // per-launch pixel offsets: the tiles' costs drift without a new view
     p.nodes = ctx->d_nodes;
     p.att = ctx->d_att;
     p.n_nodes = (uint32_t)std::min<size_t>(ctx->n_nodes, 0xFFFFFFFFu);
@@ -1030,6 +1040,11 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     p.xcd_remap = ctx->xcd_remap;
     if (p.xcd_remap == 2 && ((width + 7) / 8) % (8 * svo::STRIP_K) != 0) p.xcd_remap = 0;
     p.shadows = (ctx->options & SVO_OPT_SHADOW_RAYS) ? (ctx->shadow_compact ? 3 : ctx->fused_shadows ? 2 : 1) : 0;
+}
+
+// svo_render_samples' two forms: one sample folded into the one-sample launch, or samples in flight.
+int sample_forms(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p, const SampleArgs *sa) {
+    const Deal &b = L.b;
     if (sa && sa->n == 1) {
         // one sample: the one-sample launch itself with AddShader's blend in its store epilogue (the
         // samples kernel's S waves per tile, barrier and blend loop cost S = 1 ~13 %)
@@ -1043,7 +1058,7 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
         p.cam.px_off[0] = sa->offsets[0];   // this sample's _PixelOffset
         p.cam.px_off[1] = sa->offsets[1];
         p.shadows = 0;
-        jittered = true;
+        L.jittered = true;
         sa = nullptr;
     }
     if (sa) {   // samples in flight: primary rays only, the blend replaces every other output
@@ -1070,140 +1085,139 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
         p.out.frame_layout = sa->layout == SVO_LAYOUT_FRAME && b.count > 1 ? 1 : 0;
         p.shadows = 0;
     }
-    if (p.shadows == 3 && out.hitmask) p.shadows = 1;   // the caller's masks are not a list scratch
-    if (p.local_rows == 0) return SVO_OK;
-    const bool instr = out.fetches || out.starts;   // instrumented: svo_count_fetches / svo_beam_starts
-    if (instr) p.shadows = 0;
-    hipStream_t s = stream ? stream : ctx->stream;
+    return SVO_OK;
+}
+
+// The two-pass shadow forms' scratch (shared between the streams: order_scratch).
+int shadow_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
+    int rc;
     if ((p.shadows == 1 || p.shadows == 3) && !p.out.hits && !p.out.compact) {   // the second pass reads the records
-        int rc2 = ensure_out(ctx, (size_t)(p.out.frame_layout ? height : p.local_rows) * (size_t)width);
-        if (rc2) return rc2;
-        rc2 = order_scratch(ctx, s);
-        if (rc2) return rc2;
+        rc = ensure_out(ctx, (size_t)(p.out.frame_layout ? p.height : p.local_rows) * (size_t)p.width);
+        if (rc) return rc;
+        rc = order_scratch(ctx, L.s);
+        if (rc) return rc;
         p.out.hits = reinterpret_cast<svo::Hit *>(ctx->d_out_hits);
     }
     if (p.shadows == 3) {   // the compacted pass's masks + hit list (shared scratch, ordered like d_out_hits)
-        const size_t need = svo::shadow_list_bytes(width, p.local_rows);
+        const size_t need = svo::shadow_list_bytes(p.width, p.local_rows);
         if (ctx->shadow_list_cap < need) {
             HIP_TRY(hipDeviceSynchronize());   // an earlier launch may still read the old list
-            if (ctx->d_shadow_list) hipFree(ctx->d_shadow_list);
-            ctx->d_shadow_list = nullptr;
-            ctx->shadow_list_cap = 0;
-            HIP_TRY(hipMalloc(&ctx->d_shadow_list, need));
-            ctx->shadow_list_cap = need;
+            rc = regrow(&ctx->d_shadow_list, &ctx->shadow_list_cap, need, need);
+            if (rc) return rc;
         }
-        rc = order_scratch(ctx, s);
+        rc = order_scratch(ctx, L.s);
         if (rc) return rc;
         p.out.hitmask = reinterpret_cast<unsigned long long *>(ctx->d_shadow_list);
     }
-    p.prio = ctx->prio;
-    const bool ordered = ctx->tile_order && !instr;
-    const int n_tiles = ((width + 7) / 8) * ((p.local_rows + 7) / 8);
-    Geo key;        // the geometry (seg 0): the key of the costs and of the loop-form decision
-    Geo okey;       // the order's key: key + the seg_cap its order was built with
-    int seg_cap = 0;
-    Sched *q = nullptr;
-    if (ordered) {
-        rc = sched_for(ctx, s, &q);
-        if (rc) return rc;
-        // a new _PixelOffset at the same view (the reference's frame loop draws one every frame,
-        // RaytracingMaster.cs:35): the stored segment starts belong to another sub-pixel ray
-        if (!p.samples && q->view_prev == ctx->view_gen &&
-            (p.cam.px_off[0] != q->off_prev[0] || p.cam.px_off[1] != q->off_prev[1]))
-            jittered = true;
-        // field by field (a hash of overlapping shifted fields could match another geometry
-        // and reuse a permutation of a different tile count)
-        key.width = width;
-        key.local_rows = p.local_rows;
-        key.rows = b.rows;
-        key.rank = b.rank;
-        key.count = b.count;
-        key.xcd = p.xcd_remap;
-        key.n_tiles = n_tiles;
-        key.deal = b.key();
-        // segmented heavy tiles: primary rays of a tree pool in XCD-strip order
-        seg_cap = (ctx->seg_mode || ctx->seg_all) && p.xcd_remap == 2 && !p.guard && p.shadows == 0 && !p.samples
-                      ? (ctx->seg_all ? (n_tiles + 7) / 8 : ctx->seg_cap) : 0;
-        const size_t order_need = svo::order_strips_entries(n_tiles, seg_cap);
-        if (!q->side) {
-            HIP_TRY(hipStreamCreateWithFlags(&q->side, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&q->render_done, hipEventDisableTiming));
-            for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&q->build_ev[i], hipEventDisableTiming));
+    return SVO_OK;
+}
+
+// Cost-ordered dispatch: take the stream's Sched, key this launch's geometry and grow the buffers.
+int take_sched(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
+    const Deal &b = L.b;
+    const hipStream_t s = L.s;
+    const int n_tiles = L.n_tiles;
+    Geo &key = L.key;
+    int rc = sched_for(ctx, s, &L.q);
+    if (rc) return rc;
+    Sched *q = L.q;
+    // a new _PixelOffset at the same view (the reference's frame loop draws one every frame,
+    // RaytracingMaster.cs:35): the stored segment starts belong to another sub-pixel ray
+    if (!p.samples && q->view_prev == ctx->view_gen &&
+        (p.cam.px_off[0] != q->off_prev[0] || p.cam.px_off[1] != q->off_prev[1]))
+        L.jittered = true;
+    // field by field (a hash of overlapping shifted fields could match another geometry
+    // and reuse a permutation of a different tile count)
+    key.width = p.width;
+    key.local_rows = p.local_rows;
+    key.rows = b.rows;
+    key.rank = b.rank;
+    key.count = b.count;
+    key.xcd = p.xcd_remap;
+    key.n_tiles = n_tiles;
+    key.deal = b.key();
+    // segmented heavy tiles: primary rays of a tree pool in XCD-strip order
+    const int seg_cap = L.seg_cap =
+        (ctx->seg_mode || ctx->seg_all) && p.xcd_remap == 2 && !p.guard && p.shadows == 0 && !p.samples
+            ? (ctx->seg_all ? (n_tiles + 7) / 8 : ctx->seg_cap) : 0;
+    const size_t order_need = svo::order_strips_entries(n_tiles, seg_cap);
+    if (!q->side) {
+        HIP_TRY(hipStreamCreateWithFlags(&q->side, hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&q->render_done, hipEventDisableTiming));
+        for (int i = 0; i < 2; ++i) HIP_TRY(hipEventCreateWithFlags(&q->build_ev[i], hipEventDisableTiming));
+    }
+    if (q->cap < (size_t)n_tiles || q->order_cap < order_need) {
+        HIP_TRY(hipStreamSynchronize(s));   // a pending launch on this stream may still use the old buffers
+        HIP_TRY(hipStreamSynchronize(q->side));   // ... or an order build
+        free_sched(*q);
+        const size_t cap = svo::order_cost_capacity(n_tiles);
+        for (int i = 0; i < 2; ++i) {
+            HIP_TRY(hipMalloc(&q->cost_buf[i], cap * sizeof(uint16_t)));
+            HIP_TRY(hipMemset(q->cost_buf[i], 0, cap * sizeof(uint16_t)));
+            HIP_TRY(hipMalloc(&q->part_buf[i], svo::SEG_KMAX * cap * sizeof(uint16_t)));
+            HIP_TRY(hipMemset(q->part_buf[i], 0, svo::SEG_KMAX * cap * sizeof(uint16_t)));
+            HIP_TRY(hipMalloc(&q->order_buf[i], order_need * sizeof(uint32_t)));
         }
-        if (q->cap < (size_t)n_tiles || q->order_cap < order_need) {
-            HIP_TRY(hipStreamSynchronize(s));   // a pending launch on this stream may still use the old buffers
-            HIP_TRY(hipStreamSynchronize(q->side));   // ... or an order build
-            free_sched(*q);
-            const size_t cap = svo::order_cost_capacity(n_tiles);
-            for (int i = 0; i < 2; ++i) {
-                HIP_TRY(hipMalloc(&q->cost_buf[i], cap * sizeof(uint16_t)));
-                HIP_TRY(hipMemset(q->cost_buf[i], 0, cap * sizeof(uint16_t)));
-                HIP_TRY(hipMalloc(&q->part_buf[i], svo::SEG_KMAX * cap * sizeof(uint16_t)));
-                HIP_TRY(hipMemset(q->part_buf[i], 0, svo::SEG_KMAX * cap * sizeof(uint16_t)));
-                HIP_TRY(hipMalloc(&q->order_buf[i], order_need * sizeof(uint32_t)));
-            }
-            HIP_TRY(hipMalloc(&q->shadow_cost, cap * sizeof(uint16_t)));
-            HIP_TRY(hipMemset(q->shadow_cost, 0, cap * sizeof(uint16_t)));
-            HIP_TRY(hipMalloc(&q->shadow_order, ((size_t)n_tiles + 36) * sizeof(uint32_t)));
-            q->cap = (size_t)n_tiles;
-            q->order_cap = order_need;
-        }
-        if (seg_cap) {
-            const size_t px = (size_t)width * (size_t)p.local_rows;
-            if (q->hint_cap < px) {
-                HIP_TRY(hipStreamSynchronize(s));
-                if (q->seg_hint) hipFree(q->seg_hint);
-                q->seg_hint = nullptr;
-                q->hint_cap = 0;
-                HIP_TRY(hipMalloc(&q->seg_hint, 2 * px * sizeof(float4)));
-                HIP_TRY(hipMemset(q->seg_hint, 0xFF, 2 * px * sizeof(float4)));   // NaN: no starts yet
-                q->hint_cap = px;
-            }
-        }
-        if (!q->stats) {
-            const size_t words = 16 * Sched::STATS_RING;
-            HIP_TRY(hipHostMalloc(&q->stats, words * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
-            std::memset(q->stats, 0, words * sizeof(uint32_t));
-            for (int r = 0; r < Sched::STATS_RING; ++r)
-                HIP_TRY(hipEventCreateWithFlags(&q->stats_ev[r], hipEventDisableTiming));
-        }
-        p.tile_cost = q->cost_buf[q->launches & 1];   // this launch's costs (see Sched)
-        p.part_cost = q->part_buf[q->launches & 1];
-        if (p.shadows == 1 && ctx->shadow_order_enabled) {
-            p.shadow_cost = q->shadow_cost;
-            p.shadow_order = q->shadow_key == key ? q->shadow_order : nullptr;
+        HIP_TRY(hipMalloc(&q->shadow_cost, cap * sizeof(uint16_t)));
+        HIP_TRY(hipMemset(q->shadow_cost, 0, cap * sizeof(uint16_t)));
+        HIP_TRY(hipMalloc(&q->shadow_order, ((size_t)n_tiles + 36) * sizeof(uint32_t)));
+        q->cap = (size_t)n_tiles;
+        q->order_cap = order_need;
+    }
+    if (seg_cap) {
+        const size_t px = (size_t)p.width * (size_t)p.local_rows;
+        if (q->hint_cap < px) {
+            HIP_TRY(hipStreamSynchronize(s));
+            rc = regrow(&q->seg_hint, &q->hint_cap, 0, 2 * px * sizeof(float4));   // (the cap once it is filled)
+            if (rc) return rc;
+            HIP_TRY(hipMemset(q->seg_hint, 0xFF, 2 * px * sizeof(float4)));   // NaN: no starts yet
+            q->hint_cap = px;
         }
     }
-    // Loop form.  A launch whose total work is small against its heaviest wave -- a strong
-    // split's per-GPU band, a sky-heavy pose, a lone tile row -- is bound by that wave's serial
-    // chain, and the latency form (svo_kernel.hip trace_lat: the node kept in the stack entry,
-    // the next node loaded mid-trip, half the occupancy) runs it faster; a launch that fills
-    // the chip's wave slots many times over is bound by issue, and the lean loop's full
-    // occupancy wins.  Measured: latency form faster when the wave trips T
-    // (sum over tiles) and heaviest tile M satisfy T < 0.3 * slots * M, slots = the lean
-    // loop's resident waves on the chip.  T and M come from the order kernel of the last
-    // COMPLETED order build at this geometry (stats_ev; the host may be many launches ahead
-    // of the GPU).  Decisions of an earlier view are kept while the camera moves (one launch
-    // per view: the last frame's costs); once a build for the current view is in flight --
-    // the second launch after a move -- the host waits for it (once per view), so a jump to
-    // a different pose is never rendered with another pose's choice.
-    // The costs (and so the decision) are keyed on the render mode too: a shadowed launch's
-    // tile costs include its shadow trips.  The wait can block the host for up to a frame,
-    // once per new view (svo_rt.h, svo_render_device).
-    // The same statistics decide whether the heaviest tiles are traced as segmented rays
-    // (segments on: exactly when the launch is latency-bound, i.e. its heaviest chain and not
-    // its issued work bounds it -- a strong split's band).
-    const int mode_now = p.shadows | (stack_mode << 2);
-    // whether this launch's primary rays get beam starts (the test of the beam block below, less the
-    // per-launch camera checks)
-    const bool beam_planned = ctx->beam && q && !p.guard && !instr && ctx->depth_exact && ctx->pool_boxes &&
-                              !ctx->pool_boxes->empty();
+    if (!q->stats) {
+        const size_t words = 16 * Sched::STATS_RING;
+        HIP_TRY(hipHostMalloc(&q->stats, words * sizeof(uint32_t), hipHostMallocCoherent | hipHostMallocMapped));
+        std::memset(q->stats, 0, words * sizeof(uint32_t));
+        for (int r = 0; r < Sched::STATS_RING; ++r)
+            HIP_TRY(hipEventCreateWithFlags(&q->stats_ev[r], hipEventDisableTiming));
+    }
+    p.tile_cost = q->cost_buf[q->launches & 1];   // this launch's costs (see Sched)
+    p.part_cost = q->part_buf[q->launches & 1];
+    if (p.shadows == 1 && ctx->shadow_order_enabled) {
+        p.shadow_cost = q->shadow_cost;
+        p.shadow_order = q->shadow_key == key ? q->shadow_order : nullptr;
+    }
+    return SVO_OK;
+}
+
+// Loop form (L.latency_bound).  A launch whose total work is small against its heaviest wave -- a strong
+// split's per-GPU band, a sky-heavy pose, a lone tile row -- is bound by that wave's serial
+// chain, and the latency form (svo_kernel.hip trace_lat: the node kept in the stack entry,
+// the next node loaded mid-trip, half the occupancy) runs it faster; a launch that fills
+// the chip's wave slots many times over is bound by issue, and the lean loop's full
+// occupancy wins.  Measured: latency form faster when the wave trips T
+// (sum over tiles) and heaviest tile M satisfy T < 0.3 * slots * M, slots = the lean
+// loop's resident waves on the chip.  T and M come from the order kernel of the last
+// COMPLETED order build at this geometry (stats_ev; the host may be many launches ahead
+// of the GPU).  Decisions of an earlier view are kept while the camera moves (one launch
+// per view: the last frame's costs); once a build for the current view is in flight --
+// the second launch after a move -- the host waits for it (once per view), so a jump to
+// a different pose is never rendered with another pose's choice.
+// The costs (and so the decision) are keyed on the render mode too: a shadowed launch's
+// tile costs include its shadow trips.  The wait can block the host for up to a frame,
+// once per new view (svo_rt.h, svo_render_device).
+// The same statistics decide whether the heaviest tiles are traced as segmented rays
+// (segments on: exactly when the launch is latency-bound, i.e. its heaviest chain and not
+// its issued work bounds it -- a strong split's band).
+int decide_loop_form(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
+    Sched *q = L.q;
+    const Geo &key = L.key;
+    const int mode_now = L.mode_now;
     p.lat = 0;
-    bool latency_bound = false;
     const bool have_order = q && [&] { Geo g = q->order_key; g.seg = g.kpack = 0; return g == key; }();
-    if (!p.guard && p.shadows == 0 && !instr && !p.samples && (ctx->lat_mode != 0 || seg_cap)) {
+    if (!p.guard && p.shadows == 0 && !L.instr && !p.samples && (ctx->lat_mode != 0 || L.seg_cap)) {
         if (ctx->lat_mode == 1) {
-            latency_bound = true;
+            L.latency_bound = true;
         } else if (q && q->stats && have_order) {
             // the newest pending build first: wait for it if it is this view's and this view has
             // no decision yet (once per view), else take the newest build that has completed
@@ -1220,123 +1234,115 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
                 for (int j = i; j <= Sched::STATS_RING; ++j)   // r and every older build (newer ones stay pending)
                     q->stats_pending[(q->stats_head + Sched::STATS_RING - j) % Sched::STATS_RING] = false;
                 if (q->stats_key[r] == key && q->stats_mode[r] == mode_now) {
-                    const volatile uint32_t *st16 = q->stats + 16 * r;
-                    uint32_t m = 0;
-                    uint64_t t = 0;
-                    for (int x = 0; x < 8; ++x) {
-                        m = std::max(m, (uint32_t)st16[2 * x]);
-                        t += st16[2 * x + 1];
-                    }
-                    const size_t lds = (size_t)p.slots * svo::TILE * sizeof(uint2);
-                    const double slots = (double)ctx->num_cus * (double)std::min<size_t>(32, (160 * 1024) / lds);
+                    const svo_sched::Stats tm = svo_sched::reduce_stats(q->stats + 16 * r);
+                    const double slots = svo_sched::lean_slots(ctx->num_cus, (size_t)p.slots * svo::TILE * sizeof(uint2));
                     // with beam starts the rule picks only the class table (the loop stays lean); measured
                     // boundary 0.28: C3 bands at N = 2 (flyover 0.18, terrain-facing 0.23, Main.unity 0.27)
                     // run faster with the latency table, the flyover frame (0.30, 0.30-0.33 panning),
                     // terrain-facing (0.45) and Main.unity (0.49) with the issue table
-                    const double ratio = beam_planned ? ctx->seg_ratio : ctx->lat_ratio;
+                    const double ratio = L.beam_planned ? ctx->seg_ratio : ctx->lat_ratio;
                     // hysteresis of 15 % around it once this geometry and mode have a decision: costs
                     // measured under one class table (or with jittered rays) move T a little, and a
                     // flip near the boundary costs more than either table (the next launches find no
                     // order built for the other table's class layout)
                     const bool prior = q->lat_key == q->stats_key[r] && q->lat_mode == q->stats_mode[r];
-                    const double bound = !prior ? ratio : q->lat_cache ? ratio * 1.15 : ratio / 1.15;
-                    q->lat_cache = m > 0 && (double)t < bound * slots * (double)m ? 1 : 0;
-                    q->lat_short = m < (uint32_t)ctx->seg_min_chain;
-                    // far fewer summed trips than resident slots x the heaviest chain (a band of an 8-way
+                    // thin: far fewer summed trips than resident slots x the heaviest chain (a band of an 8-way
                     // split): the chain alone bounds the launch and eight segments shorten it most.  No
                     // hysteresis: the second build at a new geometry reads costs of the fallback order's
                     // layout (C3 Main.unity 8-way band: 0.118 once, 0.079 from then on), and a sticky
                     // decision would keep that transient (0.0417 ms against 0.0378 with eighths)
-                    q->lat_thin = q->lat_cache && (double)t < ctx->thin_ratio * slots * (double)m;
+                    const svo_sched::LoopForm f = svo_sched::loop_form(tm.T, tm.M, slots, ratio, ctx->thin_ratio,
+                                                                       ctx->seg_min_chain, prior, q->lat_cache != 0);
+                    q->lat_cache = f.lat ? 1 : 0;
+                    q->lat_short = f.is_short;
+                    q->lat_thin = f.thin;
                     q->lat_key = q->stats_key[r];
                     q->lat_view = q->stats_view[r];
                     q->lat_mode = q->stats_mode[r];
                     if (ctx->debug & 1)   // diagnostics (SVO_DEBUG bit 0): the decision and its inputs
                         std::fprintf(stderr, "svo lat: view %llu T %llu M %u slots %.0f ratio %.6f bound %.6f thin %.6f "
-                                     "beam %d -> %s%s\n", q->lat_view, (unsigned long long)t, m, slots,
-                                     m ? (double)t / (slots * (double)m) : 0.0, bound, (double)ctx->thin_ratio,
-                                     beam_planned ? 1 : 0, q->lat_cache ? "latency" : "lean", q->lat_thin ? " thin" : "");
+                                     "beam %d -> %s%s\n", q->lat_view, (unsigned long long)tm.T, tm.M, slots,
+                                     tm.M ? (double)tm.T / (slots * (double)tm.M) : 0.0, f.bound, (double)ctx->thin_ratio,
+                                     L.beam_planned ? 1 : 0, q->lat_cache ? "latency" : "lean", q->lat_thin ? " thin" : "");
                 }
                 break;
             }
-            latency_bound = q->lat_key == key && q->lat_mode == mode_now && q->lat_cache;
+            L.latency_bound = q->lat_key == key && q->lat_mode == mode_now && q->lat_cache;
         }
     }
-    int used_kpack = 0;   // the class layout of the order this launch dispatches in
-    if (q) {   // the order this launch dispatches in: with segmented heavy tiles if so decided
-        okey = key;
-        // a latency-bound launch whose heaviest chain is short (C1, C2: 76 and 111 trips) runs faster in
-        // the latency form without segments or beam starts (C2 0.041 against 0.047 ms, C1 0.025 / 0.031)
-        const bool short_chains = latency_bound && !ctx->seg_all && q->lat_short;
-        okey.kpack = ctx->seg_all ? ctx->seg_all * 0x111111 : short_chains || (jittered && ctx->seg_jitter == 0) ? 0
-                   : latency_bound ? (q->lat_thin ? ctx->seg_kpack_thin : ctx->seg_kpack_lat) : ctx->seg_kpack_issue;
-        okey.seg = seg_cap && okey.kpack ? seg_cap : 0;
-        if (!okey.seg) okey.kpack = 0;
-        // the newest build it follows by >= 2 launches (Sched): a build that launch n - 2 was
-        // followed by read the cost buffer this launch writes, so it is waited for whatever its key
-        const long long n = (long long)q->launches;
-        int use = -1;
-        for (int i = 0; i < 2; ++i) {
-            if (q->build_at[i] < 0 || q->build_at[i] > n - 2) continue;
-            if (!q->build_seen[i]) {
-                const hipError_t st = hipEventQuery(q->build_ev[i]);
-                if (st == hipErrorNotReady) HIP_TRY(hipStreamWaitEvent(s, q->build_ev[i], 0));
-                else if (st != hipSuccess) return fail(SVO_ERR_HIP, std::string("order build: ") + hipGetErrorString(st));
-                q->build_seen[i] = true;
-            }
-            if (q->build_key[i] == okey && (use < 0 || q->build_at[i] > q->build_at[use])) use = i;
-        }
-        if (use < 0) {   // none for this class table yet: the newest at this geometry, with its own table
-            for (int i = 0; i < 2; ++i) {
-                if (q->build_at[i] < 0 || q->build_at[i] > n - 2) continue;
-                Geo g = q->build_key[i];
-                if (g.seg && !okey.seg) continue;   // part entries only where this launch segments
-                g.seg = g.kpack = 0;
-                if (g == key && (use < 0 || q->build_at[i] > q->build_at[use])) use = i;
-            }
-        }
-        p.tile_order = use >= 0 ? q->order_buf[use] : nullptr;
-        if (ctx->debug & 2)   // diagnostics (SVO_DEBUG bit 1): the order and class table each launch takes
-            std::fprintf(stderr, "svo order: launch %lld view %llu latency %d kpack %x use %d built_at %lld/%lld keys %d/%d\n",
-                         n, ctx->view_gen, (int)latency_bound, okey.kpack, use, q->build_at[0], q->build_at[1],
-                         (int)(q->build_key[0] == okey), (int)(q->build_key[1] == okey));
-        const Geo &bk = use >= 0 ? q->build_key[use] : okey;   // the class layout the order was built with
-        used_kpack = bk.kpack;
-        if (p.tile_order && bk.seg) {   // the order lists part entries: the segmented kernel
-            p.seg = bk.seg;
-            p.seg_kmax = svo::seg_kmax_of(bk.kpack);
-            const bool even = (jittered && ctx->seg_jitter == 2) || (q->view_prev != ctx->view_gen && ctx->seg_move == 2);
-            p.seg_hint = even ? nullptr : q->seg_hint;
-            if (ctx->seg_scramble) p.seg_scramble = ctx->seg_scramble * 0x9E3779B9u + ++ctx->seg_launches;
-        }
+    return SVO_OK;
+}
+
+// The order this launch dispatches in (with segmented heavy tiles if so decided): the class table it
+// asks for (L.okey) and which of the two built orders it takes.
+int choose_order(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
+    Sched *q = L.q;
+    Geo &okey = L.okey;
+    okey = L.key;
+    // a latency-bound launch whose heaviest chain is short (C1, C2: 76 and 111 trips) runs faster in
+    // the latency form without segments or beam starts (C2 0.041 against 0.047 ms, C1 0.025 / 0.031)
+    const svo_sched::ClassTable ct =
+        svo_sched::class_table(ctx->seg_all, L.seg_cap, L.latency_bound, q->lat_short, q->lat_thin, L.jittered,
+                               ctx->seg_jitter, ctx->seg_kpack_lat, ctx->seg_kpack_issue, ctx->seg_kpack_thin);
+    okey.kpack = ct.kpack;
+    okey.seg = ct.seg;
+    // the newest build it follows by >= 2 launches (Sched): a build that launch n - 2 was
+    // followed by read the cost buffer this launch writes, so it is waited for whatever its key
+    const long long n = (long long)q->launches;
+    for (int i = 0; i < 2; ++i) {
+        if (q->build_at[i] < 0 || q->build_at[i] > n - 2 || q->build_seen[i]) continue;
+        const hipError_t st = hipEventQuery(q->build_ev[i]);
+        if (st == hipErrorNotReady) HIP_TRY(hipStreamWaitEvent(L.s, q->build_ev[i], 0));
+        else if (st != hipSuccess) return fail(SVO_ERR_HIP, std::string("order build: ") + hipGetErrorString(st));
+        q->build_seen[i] = true;
     }
-    // with segmented tiles the whole tiles keep the lean loop: the latency form's doubled LDS halves
-    // the resident waves of the quarters too (C3 flyover bands, profiles/r05b_seg_ab.json: N = 2
-    // 0.0804 ms with it against 0.0629 without, N = 4 0.0500 / 0.0457, N = 8 0.0388 / 0.0395)
-    p.lat = latency_bound && ctx->lat_mode != 0 && (!p.seg || ctx->lat_mode == 1) ? 1 : 0;
-    const char *log_path = ctx->wave_log_path.empty() ? nullptr : ctx->wave_log_path.c_str();
+    const int use = svo_sched::pick_build(n, q->build_at, q->build_key, okey, L.key);
+    p.tile_order = use >= 0 ? q->order_buf[use] : nullptr;
+    if (ctx->debug & 2)   // diagnostics (SVO_DEBUG bit 1): the order and class table each launch takes
+        std::fprintf(stderr, "svo order: launch %lld view %llu latency %d kpack %x use %d built_at %lld/%lld keys %d/%d\n",
+                     n, ctx->view_gen, (int)L.latency_bound, okey.kpack, use, q->build_at[0], q->build_at[1],
+                     (int)(q->build_key[0] == okey), (int)(q->build_key[1] == okey));
+    const Geo &bk = use >= 0 ? q->build_key[use] : okey;   // the class layout the order was built with
+    L.used_kpack = bk.kpack;
+    if (p.tile_order && bk.seg) {   // the order lists part entries: the segmented kernel
+        p.seg = bk.seg;
+        p.seg_kmax = svo::seg_kmax_of(bk.kpack);
+        const bool even = (L.jittered && ctx->seg_jitter == 2) || (q->view_prev != ctx->view_gen && ctx->seg_move == 2);
+        p.seg_hint = even ? nullptr : q->seg_hint;
+        if (ctx->seg_scramble) p.seg_scramble = ctx->seg_scramble * 0x9E3779B9u + ++ctx->seg_launches;
+    }
+    return SVO_OK;
+}
+
+// The per-wave record's buffer (diagnostics: SVO_WAVE_LOG; dumped after the launch, finish_launch).
+int wave_log_buffer(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
     // one record per workgroup: the tile kernel's grid, or the segmented kernel's (its part entries)
-    const size_t n_wave = p.seg ? (size_t)svo::order_strips_grid(n_tiles, p.seg, p.seg_kmax) : (size_t)n_tiles;
-    if (log_path && !instr) {
+    const size_t n_wave = L.n_wave = p.seg ? (size_t)svo::order_strips_grid(L.n_tiles, p.seg, p.seg_kmax) : (size_t)L.n_tiles;
+    if (!ctx->wave_log_path.empty() && !L.instr) {
         if (ctx->wave_log_cap < n_wave) {
             HIP_TRY(hipDeviceSynchronize());
-            if (ctx->d_wave_log) hipFree(ctx->d_wave_log);
-            ctx->d_wave_log = nullptr;
-            ctx->wave_log_cap = 0;
-            HIP_TRY(hipMalloc(&ctx->d_wave_log, n_wave * 4 * svo::WAVE_LOG_WORDS));
-            ctx->wave_log_cap = n_wave;
+            int rc = regrow(&ctx->d_wave_log, &ctx->wave_log_cap, n_wave, n_wave * 4 * svo::WAVE_LOG_WORDS);
+            if (rc) return rc;
         }
-        HIP_TRY(hipMemsetAsync(ctx->d_wave_log, 0, n_wave * 4 * svo::WAVE_LOG_WORDS, s));
+        HIP_TRY(hipMemsetAsync(ctx->d_wave_log, 0, n_wave * 4 * svo::WAVE_LOG_WORDS, L.s));
         p.wave_log = ctx->d_wave_log;
     }
-    // Beam starts: a tree pool's primary rays start at a per-tile lower bound of
-    // their hit t, splatted from the pool's boxes right before the render, on its stream.  The
-    // bounds are a function of the camera matrices, the pool and the frame size only (pixel offsets
-    // in [0, 1] are covered), so a launch at the view of this stream's previous one reuses them --
-    // a held view (the reference's accumulating camera) splats once; a moving camera every frame.
+    return SVO_OK;
+}
+
+// Beam starts: a tree pool's primary rays start at a per-tile lower bound of
+// their hit t, splatted from the pool's boxes right before the render, on its stream.  The
+// bounds are a function of the camera matrices, the pool and the frame size only (pixel offsets
+// in [0, 1] are covered), so a launch at the view of this stream's previous one reuses them --
+// a held view (the reference's accumulating camera) splats once; a moving camera every frame.
+int beam_starts(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
+    Sched *q = L.q;
+    const hipStream_t s = L.s;
+    const int width = p.width, height = p.height;
+    int rc;
     // an instrumented launch with the beam: SVO_OPT_COUNT_BEAM's fetch count, or svo_beam_starts
     const bool count_beam = (p.out.fetches && (ctx->options & SVO_OPT_COUNT_BEAM)) || p.out.starts;
-    if (ctx->beam && (q || count_beam) && !p.guard && (!instr || count_beam) && ctx->depth_exact && !p.lat) {
+    if (ctx->beam && (q || count_beam) && !p.guard && (!L.instr || count_beam) && ctx->depth_exact && !p.lat) {
         auto in01 = [](float v) { return v >= 0.0f && v <= 1.0f; };
         bool offs = in01(p.cam.px_off[0]) && in01(p.cam.px_off[1]);
         if (p.samples) {
@@ -1366,11 +1372,8 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
                 const size_t nb = boxes->size();
                 HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the old one
                 if (db.cap < nb) {
-                    if (db.d) hipFree(db.d);
-                    db.d = nullptr;
-                    db.cap = 0;
-                    HIP_TRY(hipMalloc(&db.d, nb * sizeof(uint2)));
-                    db.cap = nb;
+                    rc = regrow(&db.d, &db.cap, nb, nb * sizeof(uint2));
+                    if (rc) return rc;
                 }
                 HIP_TRY(hipMemcpy(db.d, boxes->data(), nb * sizeof(uint2), hipMemcpyHostToDevice));
                 db.n = (uint32_t)nb;
@@ -1384,11 +1387,8 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
             if (!reuse && (cap < need || gen == 0xFFFFFFFEu)) {   // (re)filled with all-ones keys: generation 0, stale
                 HIP_TRY(hipDeviceSynchronize());   // a pending launch may still read the old buffer
                 if (cap < need) {
-                    if (buf) hipFree(buf);
-                    buf = nullptr;
-                    cap = 0;
-                    HIP_TRY(hipMalloc(&buf, need * sizeof(unsigned long long)));
-                    cap = need;
+                    rc = regrow(&buf, &cap, need, need * sizeof(unsigned long long));
+                    if (rc) return rc;
                 }
                 HIP_TRY(hipMemset(buf, 0xFF, cap * sizeof(unsigned long long)));
                 gen = 0;
@@ -1426,12 +1426,22 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
             p.ts_global_off = bp.global_off;
         }
     }
+    return SVO_OK;
+}
+
+// The render launch itself, and behind it -- by the refresh rule -- the build of the order of the
+// launch after next, on the side stream.
+int render_and_reorder(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
+    Sched *q = L.q;
+    const hipStream_t s = L.s;
+    const Geo &key = L.key, &okey = L.okey;
+    const int mode_now = L.mode_now;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (!instr) {
-        rc = take_events(ctx, STAGE_KERNEL, &ev0, &ev1);
+    if (!L.instr) {
+        int rc = take_events(ctx, STAGE_KERNEL, &ev0, &ev1);
         if (rc) return rc;
     }
-    hipError_t e = svo::launch_render(p, stack_mode, s, ev0, ev1);
+    hipError_t e = svo::launch_render(p, L.stack_mode, s, ev0, ev1);
     if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("render launch: ") + hipGetErrorString(e));
     // refresh: a new geometry, every order_every-th launch while costs can drift, a change of
     // render mode, and a camera move -- right after the first launch at a view the camera then
@@ -1450,18 +1460,18 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
         // the periodic rebuild only when costs can have changed without a new view (a jittered
         // pixel offset, a new light or pool, per-launch sample offsets): a held view with nothing
         // else changed records the same costs every launch, so its order stays exact
-        const bool drift = q->built_cost != ctx->cost_gen || p.samples != 0 || jittered;
+        const bool drift = q->built_cost != ctx->cost_gen || p.samples != 0 || L.jittered;
         // a launch dispatched in an order of another class layout (the first at a new class table)
         // recorded its costs under that layout: the next build at this table comes from a launch in
         // its own layout (C3 N = 2 band: 0.059 ms with the first build kept, 0.050 with its own)
-        const bool relayout = ctx->relayout && p.tile_order && (p.seg != okey.seg || (okey.seg && p.seg_kmax != svo::seg_kmax_of(okey.kpack))
-                                               || used_kpack != okey.kpack);
+        const bool relayout = svo_sched::other_layout(ctx->relayout != 0, p.tile_order != nullptr, p.seg, p.seg_kmax, L.used_kpack,
+                                                      okey.seg, svo::seg_kmax_of(okey.kpack), okey.kpack);
         if (relayout) q->relayout_pending = true;
         const bool own_layout = !relayout && q->relayout_pending;
         // (a held view's finer re-splat shortens its rays: the order is rebuilt from that launch's costs)
-        refresh = q->order_key != okey || (n % ctx->order_every == 0 && drift) || q->built_mode != mode_now || own_layout ||
-                  q->held_splat ||
-                  (q->built_view != ctx->view_gen && (!moving || n - q->last_build >= (unsigned long long)ctx->move_every));
+        refresh = svo_sched::needs_refresh(q->order_key != okey, n, ctx->order_every, drift, q->built_mode != mode_now, own_layout,
+                                           q->held_splat, q->built_view != ctx->view_gen, moving, n - q->last_build,
+                                           ctx->move_every);
         q->held_splat = false;
         if (own_layout) q->relayout_pending = false;
         if (refresh) q->last_build = n;
@@ -1475,10 +1485,10 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
         // on the side stream, behind this launch (its costs; and every launch that read buffer bi)
         HIP_TRY(hipEventRecord(q->render_done, s));
         HIP_TRY(hipStreamWaitEvent(q->side, q->render_done, 0));
-        e = p.xcd_remap == 2 ? svo::launch_order_strips(p.tile_cost, q->order_buf[bi], n_tiles, (width + 7) / 8, q->side,
+        e = p.xcd_remap == 2 ? svo::launch_order_strips(p.tile_cost, q->order_buf[bi], L.n_tiles, (p.width + 7) / 8, q->side,
                                                         st16, okey.seg, p.part_cost, okey.kpack,
                                                         moving_build && ctx->spread ? 1 : 0)
-                             : svo::launch_order_tiles(p.tile_cost, q->order_buf[bi], n_tiles, q->side, st16);
+                             : svo::launch_order_tiles(p.tile_cost, q->order_buf[bi], L.n_tiles, q->side, st16);
         if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("tile order launch: ") + hipGetErrorString(e));
         HIP_TRY(hipEventRecord(q->build_ev[bi], q->side));
         q->build_at[bi] = (long long)q->launches - 1;   // launches was incremented above
@@ -1497,22 +1507,86 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
             q->stats_head = (r + 1) % Sched::STATS_RING;
         }
     }
+    return SVO_OK;
+}
+
+// Behind the launch: the two-pass shadow form's own order, and the wave log's dump.
+int finish_launch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
+    Sched *q = L.q;
+    const hipStream_t s = L.s;
+    const Geo &key = L.key;
     if (q && p.shadow_cost && (q->shadow_key != key || q->shadow_launches++ % ctx->order_every == 0)) {
-        e = p.xcd_remap == 2 ? svo::launch_order_strips(q->shadow_cost, q->shadow_order, n_tiles, (width + 7) / 8, s)
-                             : svo::launch_order_tiles(q->shadow_cost, q->shadow_order, n_tiles, s);
+        hipError_t e = p.xcd_remap == 2
+                           ? svo::launch_order_strips(q->shadow_cost, q->shadow_order, L.n_tiles, (p.width + 7) / 8, s)
+                           : svo::launch_order_tiles(q->shadow_cost, q->shadow_order, L.n_tiles, s);
         if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("shadow order launch: ") + hipGetErrorString(e));
         q->shadow_key = key;
     }
     if (p.wave_log) {   // blocking dump of the last launch's per-wave record
         HIP_TRY(hipStreamSynchronize(s));
-        std::vector<uint32_t> h(n_wave * svo::WAVE_LOG_WORDS);
+        std::vector<uint32_t> h(L.n_wave * svo::WAVE_LOG_WORDS);
         HIP_TRY(hipMemcpy(h.data(), ctx->d_wave_log, h.size() * 4, hipMemcpyDeviceToHost));
-        if (FILE *f = std::fopen(log_path, "wb")) {
-            std::fwrite(h.data(), 4 * svo::WAVE_LOG_WORDS, n_wave, f);
+        if (FILE *f = std::fopen(ctx->wave_log_path.c_str(), "wb")) {
+            std::fwrite(h.data(), 4 * svo::WAVE_LOG_WORDS, L.n_wave, f);
             std::fclose(f);
         }
     }
     return SVO_OK;
+}
+
+// One render launch (every entry point's, and each member's of a multi-device frame): its phases.
+int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *band, svo::Outputs out,
+           hipStream_t stream, const SampleArgs *sa = nullptr) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (width <= 0 || height <= 0) return fail(SVO_ERR_ARG, "width/height must be positive");
+    if ((size_t)width * (size_t)height > ((size_t)1 << 31)) return fail(SVO_ERR_ARG, "frame larger than 2^31 pixels");
+    if (stack_mode != SVO_STACK_HLSL && stack_mode != SVO_STACK_EXACT)
+        return fail(SVO_ERR_ARG, "unknown stack mode");
+    if (ctx->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
+    if (!ctx->cam_set) return fail(SVO_ERR_STATE, "camera not set (svo_set_camera)");
+    LaunchPlan L;
+    L.stack_mode = stack_mode;
+    int rc = check_band(band, height, &L.b);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    svo::LaunchParams p;
+    base_params(ctx, L, width, height, out, p);
+    rc = sample_forms(ctx, L, p, sa);
+    if (rc) return rc;
+    if (p.shadows == 3 && out.hitmask) p.shadows = 1;   // the caller's masks are not a list scratch
+    if (p.local_rows == 0) return SVO_OK;
+    L.instr = out.fetches || out.starts;
+    if (L.instr) p.shadows = 0;
+    L.s = stream ? stream : ctx->stream;
+    rc = shadow_scratch(ctx, L, p);
+    if (rc) return rc;
+    p.prio = ctx->prio;
+    L.n_tiles = ((width + 7) / 8) * ((p.local_rows + 7) / 8);
+    if (ctx->tile_order && !L.instr) {
+        rc = take_sched(ctx, L, p);
+        if (rc) return rc;
+    }
+    L.mode_now = p.shadows | (stack_mode << 2);
+    // whether this launch's primary rays get beam starts (beam_starts' test, less the per-launch camera checks)
+    L.beam_planned = ctx->beam && L.q && !p.guard && !L.instr && ctx->depth_exact && ctx->pool_boxes &&
+                     !ctx->pool_boxes->empty();
+    rc = decide_loop_form(ctx, L, p);
+    if (rc) return rc;
+    if (L.q) {
+        rc = choose_order(ctx, L, p);
+        if (rc) return rc;
+    }
+    // with segmented tiles the whole tiles keep the lean loop: the latency form's doubled LDS halves
+    // the resident waves of the quarters too (C3 flyover bands, profiles/r05b_seg_ab.json: N = 2
+    // 0.0804 ms with it against 0.0629 without, N = 4 0.0500 / 0.0457, N = 8 0.0388 / 0.0395)
+    p.lat = L.latency_bound && ctx->lat_mode != 0 && (!p.seg || ctx->lat_mode == 1) ? 1 : 0;
+    rc = wave_log_buffer(ctx, L, p);
+    if (rc) return rc;
+    rc = beam_starts(ctx, L, p);
+    if (rc) return rc;
+    rc = render_and_reorder(ctx, L, p);
+    if (rc) return rc;
+    return finish_launch(ctx, L, p);
 }
 
 // Enqueue the assemble kernel on this context's device (svo_assemble_frame, and
@@ -1649,11 +1723,8 @@ int multi_render(svo_ctx *ctx, int width, int height, int stack_mode, const svo_
         }
         if (fmt == SVO_PART_SPARSE_RGB8 && pr.dense_cap < (size_t)rows_i * width * 3) {
             HIP_TRY(hipStreamSynchronize(m->stream));   // an earlier pack may still read the old scratch
-            if (pr.dense) hipFree(pr.dense);
-            pr.dense = nullptr;
-            pr.dense_cap = 0;
-            HIP_TRY(hipMalloc(&pr.dense, std::max<size_t>((size_t)rows_i * width * 3, 16)));
-            pr.dense_cap = (size_t)rows_i * width * 3;
+            rc = regrow(&pr.dense, &pr.dense_cap, (size_t)rows_i * width * 3, std::max<size_t>((size_t)rows_i * width * 3, 16));
+            if (rc) return rc;
         }
         if (sa && (pr.accum_w != width || pr.accum_rows != rows_i || pr.accum_deal != dkey)) {   // this member's band accumulation
             HIP_TRY(hipStreamSynchronize(m->stream));
@@ -1961,16 +2032,12 @@ int order_query_scratch(svo_ctx *c, hipStream_t s) {
     return SVO_OK;
 }
 
-// Grow-only device scratch: *buf holds at least `need` bytes afterwards.
-int grow_query_scratch(void **buf, size_t *cap, size_t need) {
+// Grow-only query scratch: *buf holds at least `need` bytes afterwards.
+template <class T>
+int grow_query_scratch(T **buf, size_t *cap, size_t need) {
     if (need <= *cap) return SVO_OK;
     HIP_TRY(hipDeviceSynchronize());   // an earlier asynchronous query may still use the old scratch
-    if (*buf) hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    HIP_TRY(hipMalloc(buf, need));
-    *cap = need;
-    return SVO_OK;
+    return regrow(buf, cap, need, need);
 }
 
 constexpr size_t MAX_QUERY_RAYS = ((size_t)1 << 31) - 1;
@@ -2010,7 +2077,7 @@ int query_device(svo_ctx *c, const svo_ray *d_rays, size_t n_rays, int stack_mod
     if (flags & SVO_QUERY_ORDERED) {
         const size_t temp = svo::query_sort_bytes(q.n);
         if (temp == 0) return fail(SVO_ERR_HIP, "radix sort: temporary storage query failed");
-        int rc = grow_query_scratch(reinterpret_cast<void **>(&c->q_keys), &c->q_cap, 4 * n_rays * sizeof(uint32_t));
+        int rc = grow_query_scratch(&c->q_keys, &c->q_cap, 4 * n_rays * sizeof(uint32_t));
         if (rc) return rc;
         rc = grow_query_scratch(&c->q_temp, &c->q_temp_cap, temp);
         if (rc) return rc;
@@ -2315,11 +2382,8 @@ int svo_set_buffer(svo_ctx *ctx, const int32_t *desc, size_t n_desc, const uint3
     HIP_TRY(hipDeviceSynchronize());
     if (n_desc > ctx->stage_cap) {
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (ctx->d_stage) hipFree(ctx->d_stage);
-        ctx->d_stage = nullptr;
-        ctx->stage_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->d_stage, n_desc * sizeof(int32_t)));
-        ctx->stage_cap = n_desc;
+        rc = regrow(&ctx->d_stage, &ctx->stage_cap, n_desc, n_desc * sizeof(int32_t));
+        if (rc) return rc;
     }
     HIP_TRY(hipMemcpyAsync(ctx->d_stage, desc, n_desc * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
     unsigned blocks = (unsigned)((n_desc + 255) / 256);
