@@ -459,6 +459,57 @@ int svo_trace_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n_rays, int stack
 int svo_trace_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, int stack_mode,
                         uint32_t flags, svo_hit *hits, float *position, uint64_t *voxel);
 
+/* Level of detail (opt-in; off by default, and with it off every byte is what it was).
+ * Laine-Karras's "terminate if the voxel is small enough", which the reference keeps commented
+ * out (NVIDIASVO.compute:77-79).  A ray carries two non-negative finite f32 numbers:
+ *   ray_size_coef  the growth of its footprint per unit of SVO-space t,
+ *   ray_size_bias  its footprint at t = 0 in SVO units (the cube's side is 1: a world length / 32).
+ * In the walk of IntersectSVO a valid child is entered when t_min <= min(t_max, tc_max) (:75,
+ * :90).  At that point, before the leaf test (:93), the child is tested for size:
+ *   small  <=>  fl(fl(tc_max * ray_size_coef) + ray_size_bias) >= scale_exp2
+ * (two IEEE roundings, no fma; tc_max the child's exit time, :69; scale_exp2 its side; an ordered
+ * compare, NaN is false).  A small child ends the walk exactly as a leaf does: the record's
+ * parent is the descriptor holding the voxel, hit_idx its slot, hit_scale above the leaf scale,
+ * t = 2048 t_min, the normal the parent's, the colour the parent's DXT texel of that slot, flag
+ * bit 0 set.  No flag marks an inner voxel (it is readable from the pool: the parent's non-leaf
+ * bit of hit_idx), and position, voxel key and the compact record keep their definitions at
+ * hit_scale.  Deviation from Laine-Karras (documented): they test one line earlier, before the
+ * t-span test; here only children the walk would otherwise enter are tested, so a voxel the ray
+ * does not cross is never reported.
+ * (0, 0) is off.  (0, 2^-k) is a depth clamp: every voxel of side <= 2^-k is a leaf.  For a
+ * camera, ray_size_coef = pixels * 2 * |inv_proj[1][1]| / height is the footprint of `pixels`
+ * pixels at the frame's centre per unit t of a unit-length ray.
+ *
+ * svo_set_lod sets the pair of the PRIMARY rays of svo_render, svo_render_device,
+ * svo_render_frame, svo_render_samples, svo_render_progressive(_async) and svo_count_fetches (a
+ * multi-device context: of every member).  svo_beam_starts and svo_assemble_frame are not
+ * affected.  It is not a svo_config field: svo_config never changes results.  Changing the pair
+ * counts as a camera move for the dispatch-order state and restarts nothing else.  With LOD on:
+ *   - cost-ordered dispatch, XCD strips, issue priority and fetch_all work as without it;
+ *   - segmented tiles and the latency loop form are off, whatever svo_config says;
+ *   - beam starts stay on, each start bounded by a floor below which no LOD hit in a voxel
+ *     larger than the splat list's smallest box can lie; where that floor is
+ *     not positive the launch takes no beam starts;
+ *   - with SVO_OPT_SHADOW_RAYS set every render entry point returns SVO_ERR_STATE before it
+ *     enqueues anything: shadow rays with LOD are not supported.
+ * A negative, NaN or infinite number or a NULL context: SVO_ERR_ARG.  svo_get_lod: either
+ * pointer may be NULL. */
+int svo_set_lod(svo_ctx *ctx, float ray_size_coef, float ray_size_bias);   /* 0, 0 = off (default) */
+int svo_get_lod(svo_ctx *ctx, float *ray_size_coef, float *ray_size_bias);
+
+/* svo_trace_rays / svo_trace_rays_host with a LOD pair of the batch's own, applied to every ray
+ * of it: classify, clamp, the t_max filter, SVO_QUERY_ORDERED and every output rule are those of
+ * svo_trace_rays, and with (0, 0) the results are byte-identical to it.  The context's own pair
+ * (svo_set_lod) is neither read nor changed, like all other render state.  Argument errors:
+ * svo_trace_rays' and a negative, NaN or infinite number, all checked before any device is
+ * touched. */
+int svo_trace_rays_lod(svo_ctx *ctx, const svo_ray *d_rays, size_t n_rays, int stack_mode,
+                       uint32_t flags, float ray_size_coef, float ray_size_bias,
+                       const svo_query_out *out, void *stream);
+int svo_trace_rays_lod_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, int stack_mode,
+                            uint32_t flags, float ray_size_coef, float ray_size_bias,
+                            svo_hit *hits, float *position, uint64_t *voxel);
+
 /* Information about the uploaded pool. */
 int svo_get_info(svo_ctx *ctx, size_t *n_nodes, int *max_depth, int *device);
 

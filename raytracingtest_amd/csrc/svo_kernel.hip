@@ -251,7 +251,10 @@ struct LeanDiag {            // DIAG instantiation only (env SVO_WAVE_LOG)
     uint32_t fetch_trips = 0, pop_trips = 0;
 };
 
-template <int MODE, bool GUARD, bool DIAG = false, bool FETCH_ALL = false, bool COUNT = false>
+// LOD: a child the walk would enter (descend) whose footprint test
+// fl(fl(tc_max * lod_coef) + lod_bias) >= scale_exp2 holds ends the ray as a leaf does: `leaf`
+// becomes `leaf | small` below -- one multiply, one add and one compare per trip on values already live.
+template <int MODE, bool GUARD, bool DIAG = false, bool FETCH_ALL = false, bool COUNT = false, bool LOD = false>
 __device__ __forceinline__ void trace_lean(const LaunchParams &p, FRay &r, uint2 *__restrict__ stk,
                                            LeanDiag *diag = nullptr) {
     // GUARD = false (host-proven, svo_rt.hip launch / recompute_depth): one tree of
@@ -330,7 +333,8 @@ __device__ __forceinline__ void trace_lean(const LaunchParams &p, FRay &r, uint2
         const lmask in_span = LM_OF(r.t_min <= tv_max), below_h = LM_OF(tc_max < r.h);
         const uint32_t cm = r.cd16 << sh;                // valid bit -> bit 31, leaf bit -> bit 23
         const lmask descend = act & LM_OF((int32_t)cm < 0) & in_span;
-        const lmask leaf = LM_OF((cm & 0x00800000u) == 0u);
+        lmask leaf = LM_OF((cm & 0x00800000u) == 0u);
+        if (LOD) leaf |= LM_OF(tc_max * p.lod_coef + p.lod_bias >= r.sexp);   // N:77-79, two roundings
         const lmask hit = descend & leaf;                // N:93-94
         const lmask store = descend & ~leaf & below_h;
         // the overflow rule is total: every PUSH candidate below the floor, storing or not, ends the
@@ -761,10 +765,13 @@ __device__ __forceinline__ lmask after_in_group(lmask m) {
 // state are never read (seg_part: only segments up to the record holder's feed the rebalance and
 // the tile cost).  Saves the walk of the segments past a hit that comes before their stored starts
 // (a jittered sample, a moving camera: the starts are one frame old).
-template <int MODE, bool FETCH_ALL, bool SEGS = true, bool COUNT = false, int KG = 0>
+// LOD (the beam form only): trace_lean's `leaf | small`; an unarmed small voxel is stepped past like an
+// unarmed leaf (the launch floors its starts so that no LOD hit lies before them, svo_lod.h lod_floor).
+template <int MODE, bool FETCH_ALL, bool SEGS = true, bool COUNT = false, int KG = 0, bool LOD = false>
 __device__ __forceinline__ void trace_seg(const LaunchParams &p, FRay &r, uint2 *__restrict__ stk, float t_start,
                                           float t_stop, bool armed0, uint32_t &n_lane, uint32_t &armed_at,
                                           bool &stopped_lane) {
+    static_assert(!(LOD && SEGS), "the segmented trace has no LOD form");
     constexpr int STRIDE = TILE;
     const int slots = p.slots;
     for (int s = 0; s < slots; ++s) stk[s * STRIDE] = make_uint2(0u, 0u);
@@ -813,7 +820,8 @@ __device__ __forceinline__ void trace_seg(const LaunchParams &p, FRay &r, uint2 
         const lmask stop_now = SEGS ? LM_OF(tc_max >= t_stop) : (lmask)0;
         const uint32_t cm = r.cd16 << sh;
         const lmask descend = act & LM_OF((int32_t)cm < 0) & in_span;
-        const lmask leaf = LM_OF((cm & 0x00800000u) == 0u);
+        lmask leaf = LM_OF((cm & 0x00800000u) == 0u);
+        if (LOD) leaf |= LM_OF(tc_max * p.lod_coef + p.lod_bias >= r.sexp);   // N:77-79, two roundings
         const lmask inner = descend & ~leaf;
         const lmask skip = inner & before;
         const lmask hit = descend & leaf & armed;        // N:93-94, armed lanes only
@@ -931,11 +939,11 @@ __device__ __forceinline__ float beam_start(const LaunchParams &p, const FRay &f
 
 // The lean loop from a beam start (trace_seg, one segment, no stop): a lane whose cube entry lies
 // at or past the start is armed from the first trip and runs the continuous loop.
-template <int MODE, bool FA, bool COUNT = false>
+template <int MODE, bool FA, bool COUNT = false, bool LOD = false>
 __device__ __forceinline__ void trace_beam(const LaunchParams &p, FRay &f, uint2 *__restrict__ stk, float start) {
     uint32_t n_lane, armed_at;
     bool stopped;
-    trace_seg<MODE, FA, false, COUNT>(p, f, stk, start, __builtin_inff(), f.t_min >= start, n_lane, armed_at, stopped);
+    trace_seg<MODE, FA, false, COUNT, 0, LOD>(p, f, stk, start, __builtin_inff(), f.t_min >= start, n_lane, armed_at, stopped);
 }
 
 // ------------------------------------------------------------- tile kernel
@@ -964,15 +972,11 @@ __device__ __forceinline__ int strip_tile(int x, int e, int tiles_x, int tiles_y
 // COUNT: the instrumented launch (per-ray descriptor fetch counts, no outputs).
 // LAT: the latency form of the loop (trace_lat) for launches that leave wave slots empty;
 // twice the LDS (the stack entries keep their node).
-template <int MODE, bool COUNT, bool FA = false, bool SH = false, bool LAT = false>
-// SGPR budget: at .sgpr_count 80 (what the compiler chose unbounded) the hardware admitted only 7
-// of these one-wave workgroups per SIMD (wave ids 0-6, 28 per CU in the per-wave HW_ID log,
-// profiles/r03t_*), though the compiler's and the API's occupancy said 8; capped at 72 it needs 70,
-// spills nothing, and 8 waves per SIMD are resident (C3 frame -2 %, profiles/r03t_ab_sgpr_cap.txt).
-#ifndef SVO_NUM_SGPR
-#define SVO_NUM_SGPR 72
-#endif
-__global__ __launch_bounds__(TILE) __attribute__((amdgpu_num_sgpr(SVO_NUM_SGPR))) void render_tile_kernel(LaunchParams p, int tiles_x) {
+// LOD: level-of-detail termination (p.lod_coef / p.lod_bias) in the primary rays' loop -- kernels of
+// their own (render_tile_lod_kernel below), so the forms without it compile to what they were.
+template <int MODE, bool COUNT, bool FA, bool SH, bool LAT, bool LOD>
+__device__ __forceinline__ void render_tile_body(const LaunchParams &p, int tiles_x) {
+    static_assert(!(LOD && (SH || LAT)), "no LOD form of the fused shadow pass or the latency loop");
     extern __shared__ uint2 stk_base[];   // [p.slots][64] (LAT: twice, the nodes behind)
     const int lane = threadIdx.x;
     const uint32_t t_entry = !COUNT && p.wave_log ? (uint32_t)__builtin_amdgcn_s_memrealtime() : 0u;
@@ -1008,7 +1012,16 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_num_sgpr(SVO_NUM_SGPR))
     FRay f;
     to_fray(r, f);
     LeanDiag dg;
-    if (COUNT) {
+    if (LOD) {   // the same choice of loop as below; a beam start never passes the launch's LOD floor
+        if (COUNT) {
+            if (p.tile_start) trace_beam<MODE, false, true, true>(p, f, stk, fminf(beam_start(p, f, x, gy), p.lod_floor));
+            else trace_lean<MODE, true, false, false, true, true>(p, f, stk);
+        }
+        else if (p.guard) trace_lean<MODE, true, false, false, false, true>(p, f, stk);
+        else if (p.tile_start) trace_beam<MODE, FA, false, true>(p, f, stk, fminf(beam_start(p, f, x, gy), p.lod_floor));
+        else trace_lean<MODE, false, false, FA, false, true>(p, f, stk);
+    }
+    else if (COUNT) {
         if (p.tile_start) trace_beam<MODE, false, true>(p, f, stk, beam_start(p, f, x, gy));   // SVO_OPT_COUNT_BEAM
         else trace_lean<MODE, true, false, false, true>(p, f, stk);
     }
@@ -1072,6 +1085,25 @@ __global__ __launch_bounds__(TILE) __attribute__((amdgpu_num_sgpr(SVO_NUM_SGPR))
     }
     store_outputs(p.out, out_index(p, lr, gy, x), o, acc);
     if (p.wave_log && lane == 0) p.wave_log[WAVE_LOG_WORDS * (size_t)blockIdx.x + 9] = (uint32_t)__builtin_amdgcn_s_memrealtime();
+}
+
+template <int MODE, bool COUNT, bool FA = false, bool SH = false, bool LAT = false>
+// SGPR budget: at .sgpr_count 80 (what the compiler chose unbounded) the hardware admitted only 7
+// of these one-wave workgroups per SIMD (wave ids 0-6, 28 per CU in the per-wave HW_ID log,
+// profiles/r03t_*), though the compiler's and the API's occupancy said 8; capped at 72 it needs 70,
+// spills nothing, and 8 waves per SIMD are resident (C3 frame -2 %, profiles/r03t_ab_sgpr_cap.txt).
+#ifndef SVO_NUM_SGPR
+#define SVO_NUM_SGPR 72
+#endif
+__global__ __launch_bounds__(TILE) __attribute__((amdgpu_num_sgpr(SVO_NUM_SGPR))) void render_tile_kernel(LaunchParams p, int tiles_x) {
+    render_tile_body<MODE, COUNT, FA, SH, LAT, false>(p, tiles_x);
+}
+
+// The LOD forms: both stack modes, FA on and off, guard or not (a launch-uniform branch), and COUNT.
+template <int MODE, bool COUNT, bool FA = false>
+__global__ __launch_bounds__(TILE) __attribute__((amdgpu_num_sgpr(SVO_NUM_SGPR), amdgpu_waves_per_eu(8, 8)))
+void render_tile_lod_kernel(LaunchParams p, int tiles_x) {
+    render_tile_body<MODE, COUNT, FA, false, false, true>(p, tiles_x);
 }
 
 // a ray's K segments are K consecutive lanes (K = 4 or 8, wave-uniform)
@@ -1330,9 +1362,8 @@ void render_seg_kernel(LaunchParams p, int tiles_x) {
 // parks its colour in its own (dead) stack region, and wave 0 blends the S colours into the
 // accumulation in sample order with accumulate_kernel's arithmetic (bit-identical to S
 // consecutive svo_accumulate calls), then stores the display words.
-template <int MODE, bool FA>
-__global__ __launch_bounds__(TILE * MAX_SAMPLES) __attribute__((amdgpu_num_sgpr(SVO_NUM_SGPR)))
-void render_samples_kernel(LaunchParams p, int tiles_x) {
+template <int MODE, bool FA, bool LOD>
+__device__ __forceinline__ void render_samples_body(const LaunchParams &p, int tiles_x) {
     extern __shared__ uint2 stk_base[];   // [sample][p.slots][64]
     const int lane = threadIdx.x & (TILE - 1);
     const int k = threadIdx.x / TILE;     // this wave's sample
@@ -1373,7 +1404,12 @@ void render_samples_kernel(LaunchParams p, int tiles_x) {
     if (k == 0 && inside) dprev = p.accum[out_index(p, lr, gy, x)];
     FRay f;
     to_fray(r, f);
-    if (p.guard) trace_lean<MODE, true>(p, f, stk);
+    if (LOD) {
+        if (p.guard) trace_lean<MODE, true, false, false, false, true>(p, f, stk);
+        else if (p.tile_start) trace_beam<MODE, FA, false, true>(p, f, stk, fminf(beam_start(p, f, x, gy), p.lod_floor));
+        else trace_lean<MODE, false, false, FA, false, true>(p, f, stk);
+    }
+    else if (p.guard) trace_lean<MODE, true>(p, f, stk);
     else if (p.tile_start) trace_beam<MODE, FA>(p, f, stk, beam_start(p, f, x, gy));
     else trace_lean<MODE, false, false, FA>(p, f, stk);
     from_fray(f, r);
@@ -1408,6 +1444,18 @@ void render_samples_kernel(LaunchParams p, int tiles_x) {
             c[2] = (uint8_t)(w >> 16);
         }
     }
+}
+
+template <int MODE, bool FA>
+__global__ __launch_bounds__(TILE * MAX_SAMPLES) __attribute__((amdgpu_num_sgpr(SVO_NUM_SGPR)))
+void render_samples_kernel(LaunchParams p, int tiles_x) {
+    render_samples_body<MODE, FA, false>(p, tiles_x);
+}
+
+template <int MODE, bool FA>
+__global__ __launch_bounds__(TILE * MAX_SAMPLES) __attribute__((amdgpu_num_sgpr(SVO_NUM_SGPR)))
+void render_samples_lod_kernel(LaunchParams p, int tiles_x) {
+    render_samples_body<MODE, FA, true>(p, tiles_x);
 }
 
 // ------------------------------------------------------------- shadow pass
@@ -1581,8 +1629,9 @@ __device__ __forceinline__ void miss_record(Record &o, uint32_t flags) {
 // the ray's own (clamped) origin and direction.  t_max filters the finished record: a hit stays one
 // iff t * (1 / 64) <= t_max -- no lane retires early on it (the loop's t_min is not provably
 // monotone in f32 across ADVANCE, so an early exit could differ from this definition).
-template <int MODE, bool GUARD, bool FA>
-__global__ __launch_bounds__(TILE) void query_rays_kernel(LaunchParams p, QueryArgs q) {
+// LOD (svo_trace_rays_lod): p.lod_coef / p.lod_bias apply to every ray of the list.
+template <int MODE, bool GUARD, bool FA, bool LOD>
+__device__ __forceinline__ void query_rays_body(const LaunchParams &p, const QueryArgs &q) {
     extern __shared__ uint2 stk_base[];
     const int lane = (int)threadIdx.x;
     const uint32_t k = blockIdx.x * TILE + (uint32_t)lane;
@@ -1606,7 +1655,7 @@ __global__ __launch_bounds__(TILE) void query_rays_kernel(LaunchParams p, QueryA
     uint2 *stk = stk_base + lane;
     FRay f;
     to_fray(r, f);
-    trace_lean<MODE, GUARD, false, FA>(p, f, stk);
+    trace_lean<MODE, GUARD, false, FA, false, LOD>(p, f, stk);
     from_fray(f, r);
     record(p, r, 0, 0, o);   // p.out is empty: the hit words only (position and key below)
     bool hit = r.scale < S_MAX;
@@ -1624,6 +1673,16 @@ __global__ __launch_bounds__(TILE) void query_rays_kernel(LaunchParams p, QueryA
             if (lane == __builtin_ctzll(live)) q.out.hitmask[blockIdx.x] = m;
         }
     }
+}
+
+template <int MODE, bool GUARD, bool FA>
+__global__ __launch_bounds__(TILE) void query_rays_kernel(LaunchParams p, QueryArgs q) {
+    query_rays_body<MODE, GUARD, FA, false>(p, q);
+}
+
+template <int MODE, bool GUARD, bool FA>
+__global__ __launch_bounds__(TILE) void query_rays_lod_kernel(LaunchParams p, QueryArgs q) {
+    query_rays_body<MODE, GUARD, FA, true>(p, q);
 }
 
 // Ordered mode's placement key of every ray: octant mask << 27 | the 27-bit Morton code (9 bits
@@ -1774,6 +1833,22 @@ static hipError_t launch_variant(const LaunchParams &p, hipStream_t stream) {
     const int bx = (p.width + 7) / 8, by = (p.local_rows + 7) / 8;
     const size_t lds = (size_t)p.slots * TILE * sizeof(uint2) + lds_pad();
     const dim3 grid((unsigned)(bx * by)), block(TILE);
+    if (p.lod) {   // level of detail: its own kernels; no segmented, latency or fused-shadow form (svo_rt.hip launch)
+        if (p.seg > 0 || p.lat || p.shadows) return hipErrorInvalidValue;
+        const bool fa = p.fetch_all && !p.guard;
+        if (COUNT)
+            hipLaunchKernelGGL((render_tile_lod_kernel<MODE, true>), grid, block, lds, stream, p, bx);
+        else if (p.samples > 0) {
+            const size_t per = (size_t)std::max(p.slots, 2) * TILE * sizeof(uint2);
+            const dim3 sblock((unsigned)(TILE * p.samples));
+            if (fa) hipLaunchKernelGGL((render_samples_lod_kernel<MODE, true>), grid, sblock, per * p.samples, stream, p, bx);
+            else hipLaunchKernelGGL((render_samples_lod_kernel<MODE, false>), grid, sblock, per * p.samples, stream, p, bx);
+        } else if (fa)
+            hipLaunchKernelGGL((render_tile_lod_kernel<MODE, false, true>), grid, block, lds, stream, p, bx);
+        else
+            hipLaunchKernelGGL((render_tile_lod_kernel<MODE, false, false>), grid, block, lds, stream, p, bx);
+        return hipGetLastError();
+    }
     if (!COUNT && p.samples > 0) {   // samples in flight: S waves per tile, S stacks (>= 1 KB each: the colours)
         const size_t per = (size_t)std::max(p.slots, 2) * TILE * sizeof(uint2);
         const dim3 sblock((unsigned)(TILE * p.samples));
@@ -1820,6 +1895,15 @@ template <int MODE>
 static hipError_t launch_query_mode(const LaunchParams &p, const QueryArgs &q, hipStream_t stream) {
     const size_t lds = (size_t)p.slots * TILE * sizeof(uint2) + lds_pad();
     const dim3 grid((q.n + (uint32_t)TILE - 1u) / (uint32_t)TILE), block(TILE);
+    if (p.lod) {
+        if (p.guard)
+            hipLaunchKernelGGL((query_rays_lod_kernel<MODE, true, false>), grid, block, lds, stream, p, q);
+        else if (p.fetch_all)
+            hipLaunchKernelGGL((query_rays_lod_kernel<MODE, false, true>), grid, block, lds, stream, p, q);
+        else
+            hipLaunchKernelGGL((query_rays_lod_kernel<MODE, false, false>), grid, block, lds, stream, p, q);
+        return hipGetLastError();
+    }
     if (p.guard)
         hipLaunchKernelGGL((query_rays_kernel<MODE, true, false>), grid, block, lds, stream, p, q);
     else if (p.fetch_all)

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "svo_rt.h"
+#include "svo_lod.h"
 #include "svo_sched.h"
 #include "svo_traverse.h"
 
@@ -254,6 +255,10 @@ struct svo_ctx {
     // ... and the finer one a held view re-splats with (beam_back_held; the same list when equal)
     std::shared_ptr<const std::vector<uint2>> pool_boxes_held;
     uint64_t pool_boxes_held_id = 0;
+    // the finest box of each list as its depth (side 2^-depth; recompute_pool): the LOD floor's s_min
+    int pool_boxes_fine = 0, pool_boxes_held_fine = 0;
+    // level of detail of the primary rays (svo_set_lod; 0, 0: off -- DESIGN.md 3.1f)
+    float lod_coef = 0.0f, lod_bias = 0.0f;
     // diagnostics (the library's only environment switches, read once at svo_create):
     // SVO_DEBUG bit 0 the loop-form / class-table decision trace, bit 1 the order each launch
     // takes; SVO_WAVE_LOG=<file> the per-wave record; SVO_BEAM_DIAG the splat's timing variants
@@ -608,6 +613,15 @@ std::shared_ptr<const std::vector<uint2>> build_beam_boxes(const uint32_t *lo, c
     return out;
 }
 
+// The depth of the finest box actually in a splat list (its side s_min = 2^-depth; budget-coarsened
+// and linked pools included: whatever the walk above listed), 0 for no list.
+int finest_box_depth(const std::shared_ptr<const std::vector<uint2>> &boxes) {
+    uint32_t d = 0;
+    if (boxes)
+        for (const uint2 &b : *boxes) d = std::max(d, b.y >> 16);
+    return (int)d;
+}
+
 // The splat depth of a held view (svo_config.beam_back_held; -1: a new view's)
 int held_back(const svo_ctx *ctx) { return ctx->beam_back_held < 0 ? ctx->beam_back : ctx->beam_back_held; }
 
@@ -723,10 +737,12 @@ int recompute_pool(svo_ctx *ctx) {
     if (boxes != ctx->pool_boxes) {
         ctx->pool_boxes = boxes;
         ctx->pool_boxes_id = boxes ? next_boxes_id() : 0;
+        ctx->pool_boxes_fine = finest_box_depth(boxes);
     }
     if (held != ctx->pool_boxes_held) {
         ctx->pool_boxes_held = held;
         ctx->pool_boxes_held_id = !held ? 0 : held == boxes ? ctx->pool_boxes_id : next_boxes_id();
+        ctx->pool_boxes_held_fine = finest_box_depth(held);
     }
     ctx->pool_boxes_back = ctx->beam_back;
     return SVO_OK;
@@ -1138,7 +1154,7 @@ int take_sched(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
     key.deal = b.key();
     // segmented heavy tiles: primary rays of a tree pool in XCD-strip order
     const int seg_cap = L.seg_cap =
-        (ctx->seg_mode || ctx->seg_all) && p.xcd_remap == 2 && !p.guard && p.shadows == 0 && !p.samples
+        (ctx->seg_mode || ctx->seg_all) && p.xcd_remap == 2 && !p.guard && p.shadows == 0 && !p.samples && !p.lod
             ? (ctx->seg_all ? (n_tiles + 7) / 8 : ctx->seg_cap) : 0;
     const size_t order_need = svo::order_strips_entries(n_tiles, seg_cap);
     if (!q->side) {
@@ -1215,7 +1231,7 @@ int decide_loop_form(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
     const int mode_now = L.mode_now;
     p.lat = 0;
     const bool have_order = q && [&] { Geo g = q->order_key; g.seg = g.kpack = 0; return g == key; }();
-    if (!p.guard && p.shadows == 0 && !L.instr && !p.samples && (ctx->lat_mode != 0 || L.seg_cap)) {
+    if (!p.guard && p.shadows == 0 && !L.instr && !p.samples && !p.lod && (ctx->lat_mode != 0 || L.seg_cap)) {
         if (ctx->lat_mode == 1) {
             L.latency_bound = true;
         } else if (q && q->stats && have_order) {
@@ -1367,7 +1383,13 @@ int beam_starts(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
         const std::shared_ptr<const std::vector<uint2>> &boxes = li ? ctx->pool_boxes_held : ctx->pool_boxes;
         const uint64_t bid = li ? ctx->pool_boxes_held_id : ctx->pool_boxes_id;
         DevBoxes &db = ctx->dev_boxes[li];
-        if (boxes && !boxes->empty() && offs && beam_camera(p.cam, width, height, &bp)) {
+        // a LOD launch: no start may pass the floor of the list it splats (svo_lod.h lod_floor);
+        // -inf: nothing to gain, no splat and no beam starts
+        const float floor = p.lod ? svo_lod::lod_floor((double)p.lod_coef, (double)p.lod_bias,
+                                                         li ? ctx->pool_boxes_held_fine : ctx->pool_boxes_fine)
+                                  : std::numeric_limits<float>::infinity();
+        if (boxes && !boxes->empty() && offs && !(floor < 0.0f) && beam_camera(p.cam, width, height, &bp)) {
+            p.lod_floor = floor;
             if (db.id != bid) {   // the device copy of this splat list
                 const size_t nb = boxes->size();
                 HIP_TRY(hipDeviceSynchronize());   // launches on any stream may still read the old one
@@ -1544,6 +1566,10 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
         return fail(SVO_ERR_ARG, "unknown stack mode");
     if (ctx->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
     if (!ctx->cam_set) return fail(SVO_ERR_STATE, "camera not set (svo_set_camera)");
+    // level of detail (svo_set_lod) applies to every launch's primary rays but svo_beam_starts' diagnostics
+    const bool lod = (ctx->lod_coef != 0.0f || ctx->lod_bias != 0.0f) && !out.starts;
+    if (lod && (ctx->options & SVO_OPT_SHADOW_RAYS))
+        return fail(SVO_ERR_STATE, "shadow rays with LOD are not supported");
     LaunchPlan L;
     L.stack_mode = stack_mode;
     int rc = check_band(band, height, &L.b);
@@ -1551,6 +1577,12 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     HIP_TRY(hipSetDevice(ctx->device));
     svo::LaunchParams p;
     base_params(ctx, L, width, height, out, p);
+    // a LOD launch takes the LOD kernels: no segmented tiles and no latency form whatever svo_config
+    // says (take_sched, decide_loop_form), beam starts floored (beam_starts)
+    p.lod = lod ? 1 : 0;
+    p.lod_coef = lod ? ctx->lod_coef : 0.0f;
+    p.lod_bias = lod ? ctx->lod_bias : 0.0f;
+    p.lod_floor = std::numeric_limits<float>::infinity();
     rc = sample_forms(ctx, L, p, sa);
     if (rc) return rc;
     if (p.shadows == 3 && out.hitmask) p.shadows = 1;   // the caller's masks are not a list scratch
@@ -2042,6 +2074,10 @@ int grow_query_scratch(T **buf, size_t *cap, size_t need) {
 
 constexpr size_t MAX_QUERY_RAYS = ((size_t)1 << 31) - 1;
 
+// A LOD pair (svo_set_lod, svo_trace_rays_lod): two non-negative finite numbers (-0 counts as 0).
+bool lod_pair_ok(float coef, float bias) { return std::isfinite(coef) && std::isfinite(bias) && coef >= 0.0f && bias >= 0.0f; }
+const char *const LOD_PAIR_MSG = "ray_size_coef and ray_size_bias must be finite and not negative";
+
 // The argument checks of both entry points that need no device and no context state.
 int check_query_args(size_t n_rays, int stack_mode, uint32_t flags) {
     if (flags & ~(uint32_t)(SVO_QUERY_ORDERED | SVO_QUERY_RAW_DIRECTIONS)) return fail(SVO_ERR_ARG, "unknown query flag bits");
@@ -2052,7 +2088,7 @@ int check_query_args(size_t n_rays, int stack_mode, uint32_t flags) {
 
 // One query on context c (single-device), its device selected: arguments checked by the caller.
 int query_device(svo_ctx *c, const svo_ray *d_rays, size_t n_rays, int stack_mode, uint32_t flags,
-                 const svo_query_out &out, hipStream_t s) {
+                 const svo_query_out &out, hipStream_t s, float lod_coef, float lod_bias) {
     if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
     if ((uintptr_t)d_rays & 15u) return fail(SVO_ERR_ARG, "d_rays must be 16-byte aligned");
     svo::LaunchParams p;
@@ -2065,6 +2101,10 @@ int query_device(svo_ctx *c, const svo_ray *d_rays, size_t n_rays, int stack_mod
     p.slots = std::max(c->depth - 1, 1);
     p.guard = !c->depth_exact || (stack_mode == 0 && c->n_nodes > ((size_t)1 << 24)) || c->n_nodes >= ((size_t)1 << 29);
     p.fetch_all = c->fetch_all >= 0 ? c->fetch_all : (c->n_nodes < ((size_t)1 << 24) ? 1 : 0);
+    // the batch's own level of detail (svo_trace_rays_lod; 0, 0: the plain kernels)
+    p.lod = lod_coef != 0.0f || lod_bias != 0.0f;
+    p.lod_coef = lod_coef;
+    p.lod_bias = lod_bias;
     svo::QueryArgs q;
     std::memset(&q, 0, sizeof q);
     q.rays = reinterpret_cast<const svo::QueryRay *>(d_rays);
@@ -2100,7 +2140,13 @@ extern "C" {
 
 int svo_trace_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n_rays, int stack_mode, uint32_t flags,
                    const svo_query_out *out, void *stream) {
+    return svo_trace_rays_lod(ctx, d_rays, n_rays, stack_mode, flags, 0.0f, 0.0f, out, stream);
+}
+
+int svo_trace_rays_lod(svo_ctx *ctx, const svo_ray *d_rays, size_t n_rays, int stack_mode, uint32_t flags,
+                       float ray_size_coef, float ray_size_bias, const svo_query_out *out, void *stream) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!lod_pair_ok(ray_size_coef, ray_size_bias)) return fail(SVO_ERR_ARG, LOD_PAIR_MSG);
     if (!d_rays) return fail(SVO_ERR_ARG, "null ray list");
     if (!out) return fail(SVO_ERR_ARG, "null svo_query_out");
     if (!out->hits && !out->position && !out->voxel && !out->hitmask) return fail(SVO_ERR_ARG, "every query output is null");
@@ -2111,7 +2157,8 @@ int svo_trace_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n_rays, int stack
         svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
         if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
         HIP_TRY(hipSetDevice(c->device));
-        return query_device(c, d_rays, n_rays, stack_mode, flags, *out, stream ? (hipStream_t)stream : c->stream);
+        return query_device(c, d_rays, n_rays, stack_mode, flags, *out, stream ? (hipStream_t)stream : c->stream,
+                            ray_size_coef, ray_size_bias);
     } catch (const std::exception &e) {
         return fail(SVO_ERR_HIP, std::string("svo_trace_rays: ") + e.what());
     }
@@ -2119,7 +2166,13 @@ int svo_trace_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n_rays, int stack
 
 int svo_trace_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, int stack_mode, uint32_t flags,
                         svo_hit *hits, float *position, uint64_t *voxel) {
+    return svo_trace_rays_lod_host(ctx, rays, n_rays, stack_mode, flags, 0.0f, 0.0f, hits, position, voxel);
+}
+
+int svo_trace_rays_lod_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, int stack_mode, uint32_t flags,
+                            float ray_size_coef, float ray_size_bias, svo_hit *hits, float *position, uint64_t *voxel) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!lod_pair_ok(ray_size_coef, ray_size_bias)) return fail(SVO_ERR_ARG, LOD_PAIR_MSG);
     if (!rays) return fail(SVO_ERR_ARG, "null ray list");
     if (!hits && !position && !voxel) return fail(SVO_ERR_ARG, "every query output is null");
     int rc = check_query_args(n_rays, stack_mode, flags);
@@ -2148,7 +2201,8 @@ int svo_trace_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, int st
         out.hits = hits ? reinterpret_cast<svo_hit *>(base + off_hits) : nullptr;
         out.position = position ? reinterpret_cast<float *>(base + off_pos) : nullptr;
         out.voxel = voxel ? reinterpret_cast<uint64_t *>(base + off_vox) : nullptr;
-        rc = query_device(c, reinterpret_cast<const svo_ray *>(base), n, stack_mode, flags, out, c->stream);
+        rc = query_device(c, reinterpret_cast<const svo_ray *>(base), n, stack_mode, flags, out, c->stream,
+                          ray_size_coef, ray_size_bias);
         if (rc) return rc;
         if (hits) HIP_TRY(hipMemcpyAsync(hits, out.hits, 24 * n, hipMemcpyDeviceToHost, c->stream));
         if (position) HIP_TRY(hipMemcpyAsync(position, out.position, 16 * n, hipMemcpyDeviceToHost, c->stream));
@@ -2445,6 +2499,26 @@ int svo_set_camera(svo_ctx *ctx, const float c2w[16], const float inv_proj[16], 
     ctx->cam.px_off[1] = px_off_y;
     std::memcpy(ctx->cam.light, light, sizeof(ctx->cam.light));
     ctx->cam_set = true;
+    return SVO_OK;
+}
+
+int svo_set_lod(svo_ctx *ctx, float ray_size_coef, float ray_size_bias) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!lod_pair_ok(ray_size_coef, ray_size_bias)) return fail(SVO_ERR_ARG, LOD_PAIR_MSG);
+    for (svo_ctx *m : ctx->members) svo_set_lod(m, ray_size_coef, ray_size_bias);
+    ray_size_coef += 0.0f;   // -0 -> +0
+    ray_size_bias += 0.0f;
+    // another pair: other hits and other tile costs -- the streams' orders rebuild as after a camera move
+    if (ctx->lod_coef != ray_size_coef || ctx->lod_bias != ray_size_bias) ++ctx->view_gen;
+    ctx->lod_coef = ray_size_coef;
+    ctx->lod_bias = ray_size_bias;
+    return SVO_OK;
+}
+
+int svo_get_lod(svo_ctx *ctx, float *ray_size_coef, float *ray_size_bias) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (ray_size_coef) *ray_size_coef = ctx->lod_coef;
+    if (ray_size_bias) *ray_size_bias = ctx->lod_bias;
     return SVO_OK;
 }
 

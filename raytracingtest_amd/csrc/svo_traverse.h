@@ -133,6 +133,12 @@ struct LaunchParams {
     const unsigned long long *tile_start;
     int ts_tiles_x, ts_super_x, ts_super_off, ts_global_off;
     uint32_t ts_gen;
+    // Level of detail (lod != 0 selects the LOD instantiations): a valid child the
+    // walk would enter ends it like a leaf when fl(fl(tc_max * lod_coef) + lod_bias) >= scale_exp2.
+    // lod_floor: no LOD hit in a voxel larger than the splat list's smallest box starts before it, so
+    // a primary ray starts at min(beam start, lod_floor) (+inf: the beam start alone).
+    int lod;
+    float lod_coef, lod_bias, lod_floor;
 };
 
 constexpr int SEG_KMAX = 8;                 // segments per ray: 4 (a lane quad) or 8, by cost class

@@ -148,6 +148,22 @@ class RaytracingMaster:
         reference's commented-out test, RaytraceCompute.compute:105-112)."""
         self._set_option(_lib.SVO_OPT_SHADOW_RAYS, enable)
 
+    def SetLod(self, ray_size_coef, ray_size_bias=0.0):
+        """Level-of-detail termination of the primary rays (svo_set_lod; Laine-Karras's test, commented
+        out at NVIDIASVO.compute:77-79): a voxel whose side is at most tc_max * ray_size_coef +
+        ray_size_bias ends the walk like a leaf.  ray_size_coef: lod.pixel_footprint(inv_proj, height,
+        pixels); ray_size_bias in SVO units (a world length / 32).  (0, 0): off, the default."""
+        before = self.GetLod()
+        check(_lib.lib().svo_set_lod(self._ctx, float(ray_size_coef), float(ray_size_bias)), "svo_set_lod")
+        if self.GetLod() != before:   # another image: the accumulation restarts, as after a camera move
+            self.currentSample = 0
+
+    def GetLod(self):
+        """(ray_size_coef, ray_size_bias) of the context (svo_get_lod)."""
+        c, b = ctypes.c_float(), ctypes.c_float()
+        check(_lib.lib().svo_get_lod(self._ctx, ctypes.byref(c), ctypes.byref(b)), "svo_get_lod")
+        return c.value, b.value
+
     def set_count_beam(self, enable=True):
         """SVO_OPT_COUNT_BEAM: count_fetches_device counts the fetches of the walk the render runs
         (from the beam start) instead of the reference's walk from the cube entry."""
@@ -347,7 +363,7 @@ class RaytracingMaster:
         return (_lib.QUERY_ORDERED if ordered else 0) | (_lib.QUERY_RAW_DIRECTIONS if raw else 0)
 
     def TraceRays(self, origins, dirs=None, t_max=None, stack_mode=STACK_HLSL, ordered=False, raw=False,
-                  want_position=False, want_voxel=False):
+                  want_position=False, want_voxel=False, lod=None):
         """Trace a batch of world-space rays through the SVO (svo_trace_rays_host; the reference's
         CPU-side SVO.Trace(Ray), Interfaces.cs:6-15): picking, line of sight, secondary rays.
         origins, dirs: [n, 3] (a direction is used as given, not normalised), or origins an
@@ -355,7 +371,9 @@ class RaytracingMaster:
         world-space parameter limit (None: no limit).  Each ray is classified and its small
         direction components clamped before it is traced (query.sanitize_rays; raw=True:
         no clamp).  ordered=True traces the rays sorted by octant and entry point: the same
-        results (measured slower with its sort included).  Blocking.  Returns the hit records
+        results (measured slower with its sort included).  lod=(ray_size_coef,
+        ray_size_bias): level-of-detail termination for every ray of the batch (svo_trace_rays_lod_host;
+        the context's own pair, SetLod, is not involved).  Blocking.  Returns the hit records
         (HIT_DTYPE [n]; t / 64 = the ray parameter of the hit; flag 0x10: invalid ray), or
         (hits, position [n, 4] or None, voxel keys [n] or None) when either is asked for."""
         from .query import make_rays
@@ -370,20 +388,30 @@ class RaytracingMaster:
         hits = np.zeros(n, HIT_DTYPE)
         pos = np.zeros((n, 4), np.float32) if want_position else None
         vox = np.zeros(n, np.uint64) if want_voxel else None
-        check(_lib.lib().svo_trace_rays_host(self._ctx, rays.ctypes.data, n, stack_mode, self._query_flags(ordered, raw),
-                                             hits.ctypes.data, None if pos is None else pos.ctypes.data,
-                                             None if vox is None else vox.ctypes.data), "svo_trace_rays_host")
+        outs = (hits.ctypes.data, None if pos is None else pos.ctypes.data, None if vox is None else vox.ctypes.data)
+        flags = self._query_flags(ordered, raw)
+        if lod is None:
+            check(_lib.lib().svo_trace_rays_host(self._ctx, rays.ctypes.data, n, stack_mode, flags, *outs),
+                  "svo_trace_rays_host")
+        else:
+            check(_lib.lib().svo_trace_rays_lod_host(self._ctx, rays.ctypes.data, n, stack_mode, flags, float(lod[0]),
+                                                     float(lod[1]), *outs), "svo_trace_rays_lod_host")
         return (hits, pos, vox) if (want_position or want_voxel) else hits
 
     def trace_rays_device(self, rays_ptr, n, hits=None, position=None, voxel=None, hitmask=None,
-                          stack_mode=STACK_HLSL, ordered=False, raw=False, stream=None):
+                          stack_mode=STACK_HLSL, ordered=False, raw=False, stream=None, lod=None):
         """Asynchronous ray query on device buffers (svo_trace_rays): rays_ptr = n svo_ray
         records (32 bytes each, 16-byte aligned); hits (n x 24 bytes), position (n float4),
         voxel (n uint64) and hitmask (ceil(n / 64) uint64) are raw device pointers, each
-        nullable, and are fully written."""
+        nullable, and are fully written.  lod=(ray_size_coef, ray_size_bias): svo_trace_rays_lod."""
         out = _lib.SvoQueryOut(hits, position, voxel, hitmask)
-        check(_lib.lib().svo_trace_rays(self._ctx, rays_ptr, int(n), stack_mode, self._query_flags(ordered, raw),
-                                        ctypes.byref(out), stream), "svo_trace_rays")
+        flags = self._query_flags(ordered, raw)
+        if lod is None:
+            check(_lib.lib().svo_trace_rays(self._ctx, rays_ptr, int(n), stack_mode, flags, ctypes.byref(out), stream),
+                  "svo_trace_rays")
+        else:
+            check(_lib.lib().svo_trace_rays_lod(self._ctx, rays_ptr, int(n), stack_mode, flags, float(lod[0]), float(lod[1]),
+                                                ctypes.byref(out), stream), "svo_trace_rays_lod")
 
     def beam_starts_device(self, width, height, starts_ptr, band=None, stream=None):
         """svo_beam_starts: every primary ray's beam start (SVO-space t, -inf: the cube entry) into a

@@ -80,6 +80,16 @@ public static class SvoNative {
     [DllImport(Lib)] public static extern int svo_trace_rays_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr nRays,
                                                                   int stackMode, uint flags, [Out] SvoHit[] hits,
                                                                   [Out] float[] position, [Out] ulong[] voxel);
+    // Level of detail (svo_rt.h): the primary rays' pair of the context, and queries with a pair of their own
+    [DllImport(Lib)] public static extern int svo_set_lod(IntPtr ctx, float raySizeCoef, float raySizeBias);
+    [DllImport(Lib)] public static extern int svo_get_lod(IntPtr ctx, out float raySizeCoef, out float raySizeBias);
+    [DllImport(Lib)] public static extern int svo_trace_rays_lod(IntPtr ctx, IntPtr dRays, UIntPtr nRays, int stackMode,
+                                                                 uint flags, float raySizeCoef, float raySizeBias,
+                                                                 ref SvoQueryOut output, IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_trace_rays_lod_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr nRays,
+                                                                      int stackMode, uint flags, float raySizeCoef,
+                                                                      float raySizeBias, [Out] SvoHit[] hits,
+                                                                      [Out] float[] position, [Out] ulong[] voxel);
 
     [StructLayout(LayoutKind.Sequential)]
     public struct SvobResult {   // == svob_result
@@ -130,6 +140,10 @@ public class RaytracingMasterNative : MonoBehaviour {
     public bool segmentedRays = true;            // segments: heavy tiles traced as exact t-segments
     public bool costOrderedDispatch = true;      // tile_order: heaviest tiles dispatched first
     [Range(1, 32)] public int moveEvery = 4;     // while the camera moves, rebuild the order every k-th frame
+    // Level of detail (svo_set_lod; NOT render policy: it changes the image): a voxel smaller than this many
+    // pixels ends the walk like a leaf.  0 = off.  Not supported together with shadow rays.
+    [Range(0, 16)] public float lodPixels = 0;
+    float _lodPixelsSet = 0;
     public enum ShadowForm { Fused = 0, TilePass = 1, CompactedList = 2 }
     public ShadowForm shadowForm = ShadowForm.Fused;
 
@@ -278,6 +292,10 @@ public class RaytracingMasterNative : MonoBehaviour {
                                                  UnityEngine.Random.value, UnityEngine.Random.value,
                                                  new[] { l.x, l.y, l.z, DirectionalLight.intensity }), "svo_set_camera");
         int w = Screen.width, h = Screen.height;
+        // ray_size_coef: the footprint of lodPixels pixels at the frame's centre per unit t of a unit ray
+        SvoNative.Check(SvoNative.svo_set_lod(_ctx, lodPixels * 2f * Mathf.Abs(_camera.projectionMatrix.inverse[1, 1]) / h, 0f),
+                        "svo_set_lod");
+        if (lodPixels != _lodPixelsSet) { _lodPixelsSet = lodPixels; _currentSample = 0; }   // another image: a fresh accumulation
         // the pipelined path moves 3-byte pixels (RGB24: a quarter fewer bytes over PCIe); `pipelined`
         // is an Inspector field, so a toggle at run time recreates the texture in the other format
         TextureFormat want = pipelined ? TextureFormat.RGB24 : TextureFormat.RGBA32;
