@@ -510,6 +510,60 @@ int svo_trace_rays_lod_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, in
                             uint32_t flags, float ray_size_coef, float ray_size_bias,
                             svo_hit *hits, float *position, uint64_t *voxel);
 
+/* Specular reflection (opt-in; off by default, and with it off every byte is what it was).
+ * The reference's CSMain runs up to 8 Trace / Shade rounds (RaytraceCompute.compute:159-166): Shade
+ * moves the ray to the hit point, reflects it and multiplies its energy by `specular` (:97-104),
+ * which the reference hard-codes to 0, so its loop runs once.
+ *
+ * The bounce rule.  Inputs: a ray as traced -- world-space origin o and direction d (a camera ray
+ * as is; any other ray's direction after the query's clamp) -- and its hit: t (the record's t),
+ * the record normal n, hit_scale s and the voxel key's integer coordinates c.  Every operation is
+ * one IEEE f32 rounding, no fma:
+ *  1. box: side = 2^(s - 18), lo_k = c_k side - 16, hi_k = lo_k + side (exact: the voxel in world space).
+ *  2. entry face: face_k = d_k > 0 ? lo_k : hi_k; te_k = (face_k - o_k) (1 / d_k); g = 0, then for
+ *     k = 1, 2: g = k if te_k > te_g (ordered: a NaN never wins); out = d_g > 0 ? -1 : +1.
+ *  3. origin: P_k = o_k + (t (1 / 64)) d_k for k != g; origin_g = face_g + out (side 2^-6).
+ *  4. direction: dn = (n_0 d_0 + n_1 d_1) + n_2 d_2; r_k = d_k - (2 dn) n_k; if r_g points into the
+ *     face (out > 0 and r_g < 0, or out < 0 and r_g > 0), r_g = -r_g.  Not renormalised.
+ *  5. the bounce ray is {origin, t_max +inf, r, 0}, traced as svo_trace_rays traces it with flags 0.
+ * Deviation (documented): the reference's origin P + 0.001 n uses the smooth normal, which on voxels
+ * very often lies on or inside the voxel just hit (INTEGRATION.md "Reflections" has the counts);
+ * here the ray leaves through the cube face it entered by and cannot re-enter that voxel.
+ *
+ * svo_bounce_rays: from a batch and its results to the next batch: out[i] = the bounce ray of
+ * rays[i] if hits[i] has flag bit 0, else the dead ray (all 32 bytes zero except t_max = +inf: a
+ * zero direction, so svo_trace_rays classifies it invalid).  flags: SVO_QUERY_RAW_DIRECTIONS only
+ * (how rays[i] was traced).  Reads no pool.  Writes nothing past n entries; d_rays_out may be
+ * d_rays.  NULL pointers, unknown flag bits or n > 2^31 - 1: SVO_ERR_ARG, checked before any device
+ * is touched; n == 0: SVO_OK, nothing launched.  Ray lists 16-byte aligned, records and keys
+ * 8-byte.  A multi-device context runs it on devices[0].  Asynchronous on `stream`; the host form
+ * blocks. */
+int svo_bounce_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
+                    const uint64_t *d_voxel, svo_ray *d_rays_out, void *stream);
+int svo_bounce_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
+                         const uint64_t *voxel, svo_ray *rays_out);
+
+/* Reflections in renders.  specular: three numbers in [0, 1]; max_bounces in 0..7 (the reference's
+ * loop is 8 rounds: the primary ray plus 7); anything else, NaN included: SVO_ERR_ARG.  NULL, all
+ * zero or max_bounces 0: off.  Not a svo_config field: svo_config never changes results.
+ * Per pixel with a primary hit (misses keep their sky): res = the pixel's colour as rendered with
+ * reflection off and e = (1, 1, 1); then for b = 1 .. max_bounces: e *= specular; stop if e is all
+ * zero; make the bounce ray of the current ray and hit; stop if it is invalid by the query's
+ * classify; trace it; col = the shaded colour of its hit (normal and DXT albedo of the new record),
+ * or the sky of the traced direction on a miss (a record without flag bit 0 is a miss);
+ * res += e col; stop on a miss, else the bounce ray and its hit become current.
+ * Only rgba, rgba8 and rgb8 change (and through them a progressive accumulation); hits, compact,
+ * position, voxel and hitmask stay the primary ray's.  The bounces are a second pass behind the
+ * primary launch, which takes exactly the path it takes with reflection off.
+ * Served: svo_render, svo_render_device, svo_render_frame (any band, layout and stream) and
+ * svo_render_progressive(_async).  svo_count_fetches, svo_beam_starts and svo_assemble_frame are
+ * unaffected.  Stated limits, each SVO_ERR_STATE before anything is enqueued: a render with
+ * SVO_OPT_SHADOW_RAYS set, a render with LOD on, svo_render_samples; and svo_set_reflection with a
+ * non-zero setting on a multi-device context (its compact parts rebuild colours on the display
+ * device).  svo_get_reflection: either pointer may be NULL. */
+int svo_set_reflection(svo_ctx *ctx, const float specular[3], int max_bounces);   /* NULL / 0 = off (default) */
+int svo_get_reflection(svo_ctx *ctx, float specular[3], int *max_bounces);
+
 /* Information about the uploaded pool. */
 int svo_get_info(svo_ctx *ctx, size_t *n_nodes, int *max_depth, int *device);
 

@@ -37,7 +37,8 @@ EXPORTS = ("svo_create", "svo_set_buffer", "svo_set_buffer_v2", "svo_set_camera"
            "svo_pack_hits", "svo_get_member_link", "svo_stage_times", "svo_render_samples",
            "svo_render_progressive_async", "svo_progressive_last", "svo_forget_stream", "svo_get_config",
            "svo_set_config", "svo_beam_starts", "svo_trace_rays", "svo_trace_rays_host", "svo_set_lod", "svo_get_lod",
-           "svo_trace_rays_lod", "svo_trace_rays_lod_host")
+           "svo_trace_rays_lod", "svo_trace_rays_lod_host", "svo_bounce_rays", "svo_bounce_rays_host",
+           "svo_set_reflection", "svo_get_reflection")
 # svo_ray: one caller-supplied ray of svo_trace_rays (world space, direction used as given)
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")])
 assert RAY_DTYPE.itemsize == 32
@@ -192,6 +193,10 @@ def lib():
         "svo_get_lod": [vp, ctypes.POINTER(f), ctypes.POINTER(f)],
         "svo_trace_rays_lod": [vp, vp, sz, i, ctypes.c_uint32, f, f, ctypes.POINTER(SvoQueryOut), vp],
         "svo_trace_rays_lod_host": [vp, vp, sz, i, ctypes.c_uint32, f, f, vp, vp, vp],
+        "svo_bounce_rays": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp],
+        "svo_bounce_rays_host": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp],
+        "svo_set_reflection": [vp, ctypes.POINTER(f), i],
+        "svo_get_reflection": [vp, ctypes.POINTER(f), ctypes.POINTER(i)],
         "svo_destroy": [vp],
         "svo_last_error": [],
         "svo_abi_version": [],

@@ -12,6 +12,7 @@
 // a persistent kernel refilling lanes from a global counter, row-band XCD
 // placement) were removed (DESIGN.md 5.1 keeps their numbers).
 #include "svo_traverse.h"
+#include "svo_reflect.h"
 
 #include <hipcub/hipcub.hpp>   // ordered ray queries: the toolchain's device radix sort (launch_query_sort)
 
@@ -1719,6 +1720,133 @@ __global__ __launch_bounds__(256) void query_keys_kernel(QueryArgs q, uint32_t *
     index[i] = i;
 }
 
+// svo_bounce_rays: from a batch and its results to the next batch (svo_reflect.h bounce_record).  One
+// thread per ray; a thread reads its own ray before it writes its own slot, so out may be rays (no
+// __restrict__ on either).  Reads no pool.
+__global__ __launch_bounds__(256) void bounce_rays_kernel(const QueryRay *rays, uint32_t n, uint32_t flags,
+                                                          const Hit *__restrict__ hits,
+                                                          const unsigned long long *__restrict__ voxel, QueryRay *out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(rays) + 2 * (size_t)i;
+    const uint4 a = src[0], b = src[1];
+    const uint2 *rec = reinterpret_cast<const uint2 *>(hits + i);
+    const uint2 h0 = rec[0], h1 = rec[1], h2 = rec[2];
+    const uint32_t ray[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
+    const uint32_t hit[6] = { h0.x, h0.y, h1.x, h1.y, h2.x, h2.y };
+    uint32_t o[8];
+    svo_reflect::bounce_record(ray, hit, voxel[i], (flags & QUERY_RAW) != 0, o);
+    uint4 *dst = reinterpret_cast<uint4 *>(out) + 2 * (size_t)i;
+    dst[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// ------------------------------------------------------- reflection pass
+// svo_set_reflection: the reference's bounce loop (R:159-166) with specular != 0, as a
+// second pass over the primary launch's compacted hit list -- shadow_list_kernel's shape, one wave per
+// 64 list entries.  A lane starts from its pixel's camera ray and primary record (out.hits, out.voxel)
+// with res = the primary colour, recomputed from the record as assemble_kernel does, and e = 1; then
+// per bounce: e *= specular (all zero: the path ends), the bounce ray of the current ray and hit
+// (svo_reflect.h), classified and clamped as a query's ray (invalid: the path ends), traced with the
+// primary rays' loop, res += e * (shade_hit of the new hit | sky of the traced direction); a miss ends
+// the path.  The wave loops while any lane's path is alive: trace_lean runs under `if (alive)` only
+// when the wave's ballot of `alive` is non-zero (its mask comes from exec and must not be empty), and
+// the loop is left on that ballot alone.  Hit pixels' colours are overwritten with plain stores; the
+// records, keys, positions and masks stay the primary ray's.
+template <int MODE, bool GUARD, bool FA>
+__global__ __launch_bounds__(TILE) void reflect_list_kernel(LaunchParams p, const uint32_t *__restrict__ list,
+                                                            const uint32_t *__restrict__ count, float sr, float sg,
+                                                            float sb, int max_bounces) {
+    extern __shared__ uint2 stk_base[];
+    const int lane = (int)threadIdx.x;
+    const uint32_t k = blockIdx.x * TILE + (uint32_t)lane;
+    const uint32_t n = *count;
+    if (blockIdx.x * TILE >= n) return;   // the whole wave
+    const bool mine = k < n;
+    const uint32_t px = mine ? list[k] : 0u;
+    const int x = (int)(px % (uint32_t)p.width), lr = (int)(px / (uint32_t)p.width);
+    const int gy = global_row(p, lr);
+    const size_t i = out_index(p, lr, gy, x);
+    float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f}, nrm[3] = {0.0f, 0.0f, 0.0f};
+    float res[3] = {0.0f, 0.0f, 0.0f}, e[3] = {1.0f, 1.0f, 1.0f}, t = 0.0f;
+    int scale = 0;
+    unsigned long long key = 0ull;
+    if (mine) {
+        const uint2 *rec = reinterpret_cast<const uint2 *>(p.out.hits + i);
+        const uint2 h0 = rec[0], h1 = rec[1], h2 = rec[2];
+        t = __uint_as_float(h1.x);
+        nrm[0] = __uint_as_float(h1.y); nrm[1] = __uint_as_float(h2.x); nrm[2] = __uint_as_float(h2.y);
+        scale = (int)((h0.y >> 8) & 0xFFu);
+        key = p.out.voxel[i];
+        camera_ray(p.cam, p.width, p.height, x, gy, o, d);
+        const uint2 a = p.att[h0.x];
+        float alb[3];
+        decode_dxt(a.x, a.y, (int)(h0.y & 0xFFu), alb);
+        shade_hit(p.cam, nrm, alb, res);
+    }
+    bool alive = mine;
+    uint2 *stk = stk_base + lane;
+#pragma nounroll
+    for (int b = 1; b <= max_bounces; ++b) {
+        if (alive) {
+            e[0] = e[0] * sr; e[1] = e[1] * sg; e[2] = e[2] * sb;
+            if (e[0] == 0.0f && e[1] == 0.0f && e[2] == 0.0f) alive = false;
+        }
+        if (alive) {
+            svo_reflect::bounce(o, d, t, nrm, scale, key, o, d);
+            bool ok = !(d[0] == 0.0f && d[1] == 0.0f && d[2] == 0.0f);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) ok = ok && finite_f32(o[c]) && finite_f32(d[c]);
+            svo_reflect::clamp_direction(d, false);
+            alive = ok;
+        }
+        if (LM_OF(alive) == 0) break;   // wave-uniform
+        if (alive) {
+            Ray r;
+            setup_ray(o, d, r);
+            FRay f;
+            to_fray(r, f);
+            trace_lean<MODE, GUARD, false, FA>(p, f, stk);
+            from_fray(f, r);
+            float col[3];
+            const bool hit = r.scale < S_MAX;
+            if (hit) {
+                const int hit_idx = r.idx ^ r.octant_mask ^ 7;
+                const uint2 a = p.att[r.parent];
+                decode_normal(a.y >> 16, nrm);
+                normalize3(nrm);
+                float alb[3];
+                decode_dxt(a.x, a.y, hit_idx, alb);
+                shade_hit(p.cam, nrm, alb, col);
+                const float t_min = r.t_min * 32.0f;
+                t = t_min * 64.0f;
+                scale = r.scale;
+                Record h;
+                hit_position(r, o, d, h);
+                key = h.key;
+            } else {
+                sky(r.dir_y, col);
+            }
+            res[0] = res[0] + e[0] * col[0];
+            res[1] = res[1] + e[1] * col[1];
+            res[2] = res[2] + e[2] * col[2];
+            alive = hit;
+        }
+    }
+    if (!mine) return;
+    if (p.out.rgba) p.out.rgba[i] = make_float4(res[0], res[1], res[2], 1.0f);
+    if (p.out.rgba8 || p.out.rgb8) {
+        const uint32_t w = pack_rgba8(res[0], res[1], res[2]);
+        if (p.out.rgba8) p.out.rgba8[i] = w;
+        if (p.out.rgb8) {
+            uint8_t *dst = p.out.rgb8 + 3 * i;
+            dst[0] = (uint8_t)w;
+            dst[1] = (uint8_t)(w >> 8);
+            dst[2] = (uint8_t)(w >> 16);
+        }
+    }
+}
+
 // ---------------------------------------------------------- frame assembly
 // svo_assemble_frame: one thread per pixel of the frame (one row per grid y).
 // Row y belongs to band b = y / band_rows and, round-robin, to part m = b % n_parts
@@ -1925,6 +2053,13 @@ hipError_t launch_query(const LaunchParams &p, const QueryArgs &q, int stack_mod
 hipError_t launch_query_keys(const QueryArgs &q, uint32_t *keys, uint32_t *index, hipStream_t stream) {
     if (q.n == 0) return hipSuccess;
     hipLaunchKernelGGL(query_keys_kernel, dim3((q.n + 255u) / 256u), dim3(256), 0, stream, q, keys, index);
+    return hipGetLastError();
+}
+
+hipError_t launch_bounce_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
+                              const unsigned long long *voxel, QueryRay *out, hipStream_t stream) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(bounce_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, rays, n, flags, hits, voxel, out);
     return hipGetLastError();
 }
 
@@ -2780,6 +2915,38 @@ hipError_t launch_render(const LaunchParams &p, int stack_mode, hipStream_t stre
         return hipGetLastError();
     }
     return hipSuccess;
+}
+
+template <int MODE>
+static hipError_t launch_reflect_mode(const LaunchParams &q, const uint32_t *list, const uint32_t *cnt, const ReflectArgs &ra,
+                                      hipStream_t stream) {
+    const size_t lds = (size_t)q.slots * TILE * sizeof(uint2);
+    const dim3 grid((unsigned)(((size_t)q.width * (size_t)q.local_rows + TILE - 1) / TILE)), block(TILE);
+    const float sr = ra.specular[0], sg = ra.specular[1], sb = ra.specular[2];
+    // guarded pools and fetch_all select the loop as shadow_list_kernel does
+    if (q.guard)
+        hipLaunchKernelGGL((reflect_list_kernel<MODE, true, false>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces);
+    else if (q.fetch_all)
+        hipLaunchKernelGGL((reflect_list_kernel<MODE, false, true>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces);
+    else
+        hipLaunchKernelGGL((reflect_list_kernel<MODE, false, false>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces);
+    return hipGetLastError();
+}
+
+hipError_t launch_reflect(const LaunchParams &p, const ReflectArgs &ra, int stack_mode, hipStream_t stream) {
+    if (!p.out.hits || !p.out.voxel || !ra.scratch || ra.max_bounces < 1 || p.width <= 0 || p.local_rows <= 0)
+        return hipErrorInvalidValue;
+    // the hit list in the scratch whose head holds the launch's hit masks
+    hipError_t e = launch_pack<true>(nullptr, p.width, p.local_rows, ra.scratch, stream);
+    if (e != hipSuccess) return e;
+    const int n = ((p.width + 7) / 8) * ((p.local_rows + 7) / 8);
+    const SparseLayout L = sparse_layout(n, p.width * p.local_rows, 4);
+    const uint8_t *base = reinterpret_cast<const uint8_t *>(ra.scratch);
+    const uint32_t *list = reinterpret_cast<const uint32_t *>(base + L.rgb);
+    const uint32_t *cnt = reinterpret_cast<const uint32_t *>(base + L.offsets) + n;
+    LaunchParams q = p;
+    q.out.hitmask = nullptr;
+    return stack_mode == 0 ? launch_reflect_mode<0>(q, list, cnt, ra, stream) : launch_reflect_mode<1>(q, list, cnt, ra, stream);
 }
 
 }  // namespace svo

@@ -259,6 +259,13 @@ struct svo_ctx {
     int pool_boxes_fine = 0, pool_boxes_held_fine = 0;
     // level of detail of the primary rays (svo_set_lod; 0, 0: off -- DESIGN.md 3.1f)
     float lod_coef = 0.0f, lod_bias = 0.0f;
+    // specular reflection bounces of the renders (svo_set_reflection; max_bounces 0 or specular 0: off --
+    // DESIGN.md 3.2c) and the pass's voxel-key scratch (the records and the hit list reuse the shadow
+    // forms' scratch: the two never run together)
+    float specular[3] = {0.0f, 0.0f, 0.0f};
+    int max_bounces = 0;
+    unsigned long long *d_refl_voxel = nullptr;
+    size_t refl_voxel_cap = 0;
     // diagnostics (the library's only environment switches, read once at svo_create):
     // SVO_DEBUG bit 0 the loop-form / class-table decision trace, bit 1 the order each launch
     // takes; SVO_WAVE_LOG=<file> the per-wave record; SVO_BEAM_DIAG the splat's timing variants
@@ -1128,6 +1135,58 @@ int shadow_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
     return SVO_OK;
 }
 
+bool reflection_on(const svo_ctx *ctx) {
+    return ctx->max_bounces > 0 && (ctx->specular[0] != 0.0f || ctx->specular[1] != 0.0f || ctx->specular[2] != 0.0f);
+}
+
+// The reflection pass's inputs: per hit pixel the record and the voxel key -- the
+// caller's outputs where it asked for them, else context-owned scratch -- and the hit list's scratch,
+// whose head the primary launch fills with its hit masks (a caller's own masks are copied there behind
+// it: *caller_mask).  Shared between the streams like the shadow forms' scratch (order_scratch).
+int reflect_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p, unsigned long long **caller_mask) {
+    int rc;
+    const size_t px = (size_t)(p.out.frame_layout ? p.height : p.local_rows) * (size_t)p.width;
+    if (!p.out.hits) {
+        rc = ensure_out(ctx, px);
+        if (rc) return rc;
+        p.out.hits = reinterpret_cast<svo::Hit *>(ctx->d_out_hits);
+    }
+    if (!p.out.voxel) {
+        if (ctx->refl_voxel_cap < px) {
+            HIP_TRY(hipDeviceSynchronize());   // an earlier launch may still read the old keys
+            rc = regrow(&ctx->d_refl_voxel, &ctx->refl_voxel_cap, px, px * sizeof(unsigned long long));
+            if (rc) return rc;
+        }
+        p.out.voxel = ctx->d_refl_voxel;
+    }
+    const size_t need = svo::shadow_list_bytes(p.width, p.local_rows);
+    if (ctx->shadow_list_cap < need) {
+        HIP_TRY(hipDeviceSynchronize());   // an earlier launch may still read the old list
+        rc = regrow(&ctx->d_shadow_list, &ctx->shadow_list_cap, need, need);
+        if (rc) return rc;
+    }
+    rc = order_scratch(ctx, L.s);
+    if (rc) return rc;
+    *caller_mask = p.out.hitmask;
+    if (!p.out.hitmask) p.out.hitmask = reinterpret_cast<unsigned long long *>(ctx->d_shadow_list);
+    return SVO_OK;
+}
+
+// Behind the primary launch: compact its hit pixels and follow each one's specular path.
+int reflect_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsigned long long *caller_mask) {
+    if (caller_mask)
+        HIP_TRY(hipMemcpyAsync(ctx->d_shadow_list, caller_mask, (size_t)L.n_tiles * sizeof(unsigned long long),
+                               hipMemcpyDeviceToDevice, L.s));
+    svo::ReflectArgs ra;
+    std::memset(&ra, 0, sizeof ra);
+    ra.scratch = ctx->d_shadow_list;
+    for (int k = 0; k < 3; ++k) ra.specular[k] = ctx->specular[k];
+    ra.max_bounces = ctx->max_bounces;
+    const hipError_t e = svo::launch_reflect(p, ra, L.stack_mode, L.s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("reflection launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
 // Cost-ordered dispatch: take the stream's Sched, key this launch's geometry and grow the buffers.
 int take_sched(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
     const Deal &b = L.b;
@@ -1570,6 +1629,13 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     const bool lod = (ctx->lod_coef != 0.0f || ctx->lod_bias != 0.0f) && !out.starts;
     if (lod && (ctx->options & SVO_OPT_SHADOW_RAYS))
         return fail(SVO_ERR_STATE, "shadow rays with LOD are not supported");
+    // reflection bounces (svo_set_reflection): a second pass behind every render launch's primary rays; the
+    // instrumented launches (svo_count_fetches, svo_beam_starts) trace primary rays only
+    const bool refl_on = reflection_on(ctx) && !out.fetches && !out.starts;
+    if (refl_on && sa) return fail(SVO_ERR_STATE, "svo_render_samples with reflection is not supported");
+    if (refl_on && (ctx->options & SVO_OPT_SHADOW_RAYS))
+        return fail(SVO_ERR_STATE, "shadow rays with reflection are not supported");
+    if (refl_on && lod) return fail(SVO_ERR_STATE, "reflection with LOD is not supported");
     LaunchPlan L;
     L.stack_mode = stack_mode;
     int rc = check_band(band, height, &L.b);
@@ -1592,6 +1658,13 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     L.s = stream ? stream : ctx->stream;
     rc = shadow_scratch(ctx, L, p);
     if (rc) return rc;
+    // only the colours change: a launch that writes none has no reflection pass
+    const bool reflect = refl_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
+    unsigned long long *caller_mask = nullptr;
+    if (reflect) {
+        rc = reflect_scratch(ctx, L, p, &caller_mask);
+        if (rc) return rc;
+    }
     p.prio = ctx->prio;
     L.n_tiles = ((width + 7) / 8) * ((p.local_rows + 7) / 8);
     if (ctx->tile_order && !L.instr) {
@@ -1618,6 +1691,10 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     if (rc) return rc;
     rc = render_and_reorder(ctx, L, p);
     if (rc) return rc;
+    if (reflect) {
+        rc = reflect_pass(ctx, L, p, caller_mask);
+        if (rc) return rc;
+    }
     return finish_launch(ctx, L, p);
 }
 
@@ -1872,6 +1949,7 @@ int destroy_single(svo_ctx *ctx) {
     if (ctx->d_att) hipFree(ctx->d_att);
     if (ctx->d_stage) hipFree(ctx->d_stage);
     if (ctx->d_shadow_list) hipFree(ctx->d_shadow_list);
+    if (ctx->d_refl_voxel) hipFree(ctx->d_refl_voxel);
     if (ctx->d_out_hits) hipFree(ctx->d_out_hits);
     if (ctx->d_out_rgba) hipFree(ctx->d_out_rgba);
     if (ctx->d_accum) hipFree(ctx->d_accum);
@@ -2134,6 +2212,30 @@ int query_device(svo_ctx *c, const svo_ray *d_rays, size_t n_rays, int stack_mod
     return SVO_OK;
 }
 
+// The argument checks of svo_bounce_rays(_host) that need no device.
+int check_bounce_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const void *hits, const void *voxel,
+                             const void *rays_out) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!rays) return fail(SVO_ERR_ARG, "null ray list");
+    if (!hits) return fail(SVO_ERR_ARG, "null hit records");
+    if (!voxel) return fail(SVO_ERR_ARG, "null voxel keys");
+    if (!rays_out) return fail(SVO_ERR_ARG, "null output ray list");
+    if (flags & ~(uint32_t)SVO_QUERY_RAW_DIRECTIONS) return fail(SVO_ERR_ARG, "unknown bounce flag bits");
+    if (n > MAX_QUERY_RAYS) return fail(SVO_ERR_ARG, "more than 2^31 - 1 rays in one batch");
+    return SVO_OK;
+}
+
+int bounce_device(const void *d_rays, size_t n, uint32_t flags, const void *d_hits, const void *d_voxel,
+                         void *d_rays_out, hipStream_t s) {
+    const hipError_t e = svo::launch_bounce_rays(reinterpret_cast<const svo::QueryRay *>(d_rays), (uint32_t)n,
+                                                 (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u,
+                                                 reinterpret_cast<const svo::Hit *>(d_hits),
+                                                 reinterpret_cast<const unsigned long long *>(d_voxel),
+                                                 reinterpret_cast<svo::QueryRay *>(d_rays_out), s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("bounce launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2211,6 +2313,54 @@ int svo_trace_rays_lod_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, in
         return SVO_OK;
     } catch (const std::exception &e) {
         return fail(SVO_ERR_HIP, std::string("svo_trace_rays_host: ") + e.what());
+    }
+}
+
+int svo_bounce_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
+                    const uint64_t *d_voxel, svo_ray *d_rays_out, void *stream) {
+    int rc = check_bounce_args(ctx, d_rays, n, flags, d_hits, d_voxel, d_rays_out);
+    if (rc) return rc;
+    if (((uintptr_t)d_rays | (uintptr_t)d_rays_out) & 15u) return fail(SVO_ERR_ARG, "ray lists must be 16-byte aligned");
+    if (((uintptr_t)d_hits | (uintptr_t)d_voxel) & 7u) return fail(SVO_ERR_ARG, "hit records and voxel keys must be 8-byte aligned");
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        return bounce_device(d_rays, n, flags, d_hits, d_voxel, d_rays_out, stream ? (hipStream_t)stream : c->stream);
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_bounce_rays: ") + e.what());
+    }
+}
+
+int svo_bounce_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
+                         const uint64_t *voxel, svo_ray *rays_out) {
+    int rc = check_bounce_args(ctx, rays, n, flags, hits, voxel, rays_out);
+    if (rc) return rc;
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        // staged layout: rays (32 B, bounced in place), hit records (24 B), voxel keys (8 B) per ray
+        const size_t off_hits = 32 * n, off_vox = 56 * n;
+        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, 64 * n);
+        if (rc) return rc;
+        rc = order_query_scratch(c, c->stream);
+        if (rc) return rc;
+        char *base = static_cast<char *>(c->q_host);
+        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
+            hipStream_t s;
+            ~Drain() { hipStreamSynchronize(s); }
+        } drain{c->stream};
+        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(base + off_hits, hits, 24 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(base + off_vox, voxel, 8 * n, hipMemcpyHostToDevice, c->stream));
+        rc = bounce_device(base, n, flags, base + off_hits, base + off_vox, base, c->stream);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(rays_out, base, 32 * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SVO_OK;
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_bounce_rays_host: ") + e.what());
     }
 }
 
@@ -2512,6 +2662,29 @@ int svo_set_lod(svo_ctx *ctx, float ray_size_coef, float ray_size_bias) {
     if (ctx->lod_coef != ray_size_coef || ctx->lod_bias != ray_size_bias) ++ctx->view_gen;
     ctx->lod_coef = ray_size_coef;
     ctx->lod_bias = ray_size_bias;
+    return SVO_OK;
+}
+
+int svo_set_reflection(svo_ctx *ctx, const float specular[3], int max_bounces) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    float s[3] = {0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < 3 && specular; ++k) {
+        if (!(specular[k] >= 0.0f && specular[k] <= 1.0f)) return fail(SVO_ERR_ARG, "specular components must lie in [0, 1]");
+        s[k] = specular[k];
+    }
+    if (max_bounces < 0 || max_bounces > 7) return fail(SVO_ERR_ARG, "max_bounces must lie in 0..7");
+    const bool on = max_bounces > 0 && (s[0] != 0.0f || s[1] != 0.0f || s[2] != 0.0f);
+    if (on && is_multi(ctx))
+        return fail(SVO_ERR_STATE, "reflection on a multi-device context is not supported");
+    for (int k = 0; k < 3; ++k) ctx->specular[k] = s[k];
+    ctx->max_bounces = max_bounces;
+    return SVO_OK;
+}
+
+int svo_get_reflection(svo_ctx *ctx, float specular[3], int *max_bounces) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    for (int k = 0; k < 3 && specular; ++k) specular[k] = ctx->specular[k];
+    if (max_bounces) *max_bounces = ctx->max_bounces;
     return SVO_OK;
 }
 

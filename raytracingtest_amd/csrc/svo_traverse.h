@@ -253,6 +253,19 @@ hipError_t launch_pack_rgba8(const float4 *src, uint32_t *dst, size_t n_px, int 
 hipError_t launch_render(const LaunchParams &p, int stack_mode, hipStream_t stream, hipEvent_t primary_start = nullptr,
                          hipEvent_t primary_end = nullptr);
 
+// Reflection pass (svo_set_reflection; svo_kernel.hip reflect_list_kernel), behind a render launch's
+// primary rays: its hit pixels are packed into a list in tile order (the compacted shadow pass's
+// machinery; `scratch`: shadow_list_bytes, its head the launch's hit masks) and one wave64 follows the
+// specular paths of 64 consecutive entries, up to max_bounces bounce rays each (svo_reflect.h).
+// p: the launch's own parameters; out.hits and out.voxel hold the primary records and keys, the
+// colour outputs among out.rgba / rgba8 / rgb8 are overwritten for the hit pixels.
+struct ReflectArgs {
+    void *scratch;
+    float specular[3];
+    int max_bounces;          // 1 .. 7
+};
+hipError_t launch_reflect(const LaunchParams &p, const ReflectArgs &ra, int stack_mode, hipStream_t stream);
+
 // Ray queries (svo_trace_rays; svo_kernel.hip query_rays_kernel): one wave64 traces 64
 // consecutive entries of a flat list of world-space rays with the primary rays' lean loop.
 struct QueryRay {             // == svo_ray
@@ -284,5 +297,9 @@ hipError_t launch_query_keys(const QueryArgs &q, uint32_t *keys, uint32_t *index
 size_t query_sort_bytes(uint32_t n);
 hipError_t launch_query_sort(const uint32_t *keys, uint32_t *keys_out, const uint32_t *index, uint32_t *index_out,
                              uint32_t n, void *temp, size_t temp_bytes, hipStream_t stream);
+// svo_bounce_rays: out[i] = the bounce ray (svo_reflect.h) of rays[i] and hits[i] / voxel[i], or the dead
+// ray without flag bit 0.  flags: QUERY_RAW.  A flat launch, one thread per ray; out may be rays.
+hipError_t launch_bounce_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
+                              const unsigned long long *voxel, QueryRay *out, hipStream_t stream);
 
 }  // namespace svo

@@ -164,6 +164,27 @@ class RaytracingMaster:
         check(_lib.lib().svo_get_lod(self._ctx, ctypes.byref(c), ctypes.byref(b)), "svo_get_lod")
         return c.value, b.value
 
+    def SetReflection(self, specular, max_bounces=7):
+        """Specular reflection bounces of the renders (svo_set_reflection; the reference's Trace /
+        Shade loop, RaytraceCompute.compute:159-166, with a non-zero `specular`): each hit pixel's
+        colour becomes the primary colour plus, per bounce b <= max_bounces (0..7), specular^b times
+        the colour the bounce ray finds (reflection.bounce_rays is the rule).  specular: three
+        numbers in [0, 1], or None for off (the default).  Only the colour outputs change."""
+        before = self.GetReflection()
+        if specular is None:
+            check(_lib.lib().svo_set_reflection(self._ctx, None, 0), "svo_set_reflection")
+        else:
+            s = (ctypes.c_float * 3)(*[float(v) for v in specular])
+            check(_lib.lib().svo_set_reflection(self._ctx, s, int(max_bounces)), "svo_set_reflection")
+        if self.GetReflection() != before:   # another image: the accumulation restarts
+            self.currentSample = 0
+
+    def GetReflection(self):
+        """((r, g, b) specular, max_bounces) of the context (svo_get_reflection)."""
+        s, n = (ctypes.c_float * 3)(), ctypes.c_int()
+        check(_lib.lib().svo_get_reflection(self._ctx, s, ctypes.byref(n)), "svo_get_reflection")
+        return (s[0], s[1], s[2]), n.value
+
     def set_count_beam(self, enable=True):
         """SVO_OPT_COUNT_BEAM: count_fetches_device counts the fetches of the walk the render runs
         (from the beam start) instead of the reference's walk from the cube entry."""
@@ -412,6 +433,29 @@ class RaytracingMaster:
         else:
             check(_lib.lib().svo_trace_rays_lod(self._ctx, rays_ptr, int(n), stack_mode, flags, float(lod[0]), float(lod[1]),
                                                 ctypes.byref(out), stream), "svo_trace_rays_lod")
+
+    def BounceRays(self, rays, hits, voxel, raw=False):
+        """From a traced batch to the next one (svo_bounce_rays_host; reflection.bounce_rays is its
+        numpy statement): rays (svo_ray records), their hit records and voxel keys as TraceRays
+        returned them; raw: whether the batch was traced with raw=True.  Returns the bounce rays
+        (RAY_DTYPE [n]): a dead ray (zero direction, invalid to TraceRays) where there was no hit."""
+        rays = np.ascontiguousarray(rays, _lib.RAY_DTYPE).reshape(-1)
+        hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+        voxel = np.ascontiguousarray(voxel, np.uint64).reshape(-1)
+        if not len(rays) == len(hits) == len(voxel):
+            raise ValueError(f"{len(rays)} rays, {len(hits)} hit records, {len(voxel)} voxel keys")
+        out = np.zeros(len(rays), _lib.RAY_DTYPE)
+        check(_lib.lib().svo_bounce_rays_host(self._ctx, rays.ctypes.data, len(rays), self._query_flags(False, raw),
+                                              hits.ctypes.data, voxel.ctypes.data, out.ctypes.data),
+              "svo_bounce_rays_host")
+        return out
+
+    def bounce_rays_device(self, rays_ptr, n, hits, voxel, out, raw=False, stream=None):
+        """Asynchronous svo_bounce_rays on device buffers: rays_ptr / out = n svo_ray records
+        (16-byte aligned; out may be rays_ptr), hits (n x 24 bytes) and voxel (n uint64) the
+        results of the batch's trace."""
+        check(_lib.lib().svo_bounce_rays(self._ctx, rays_ptr, int(n), self._query_flags(False, raw), hits, voxel, out,
+                                         stream), "svo_bounce_rays")
 
     def beam_starts_device(self, width, height, starts_ptr, band=None, stream=None):
         """svo_beam_starts: every primary ray's beam start (SVO-space t, -inf: the cube entry) into a

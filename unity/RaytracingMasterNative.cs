@@ -90,6 +90,14 @@ public static class SvoNative {
                                                                       int stackMode, uint flags, float raySizeCoef,
                                                                       float raySizeBias, [Out] SvoHit[] hits,
                                                                       [Out] float[] position, [Out] ulong[] voxel);
+    // Specular reflection (svo_rt.h): the bounce-ray building block of the ray queries, and the renders' setting
+    [DllImport(Lib)] public static extern int svo_bounce_rays(IntPtr ctx, IntPtr dRays, UIntPtr n, uint flags, IntPtr dHits,
+                                                              IntPtr dVoxel, IntPtr dRaysOut, IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_bounce_rays_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr n, uint flags,
+                                                                   [In] SvoHit[] hits, [In] ulong[] voxel,
+                                                                   [Out] SvoRay[] raysOut);
+    [DllImport(Lib)] public static extern int svo_set_reflection(IntPtr ctx, [In] float[] specular, int maxBounces);
+    [DllImport(Lib)] public static extern int svo_get_reflection(IntPtr ctx, [Out] float[] specular, out int maxBounces);
 
     [StructLayout(LayoutKind.Sequential)]
     public struct SvobResult {   // == svob_result
@@ -144,6 +152,13 @@ public class RaytracingMasterNative : MonoBehaviour {
     // pixels ends the walk like a leaf.  0 = off.  Not supported together with shadow rays.
     [Range(0, 16)] public float lodPixels = 0;
     float _lodPixelsSet = 0;
+    // Specular reflection (svo_set_reflection; it changes the image): the reference's `specular` (hard-coded 0,
+    // RaytraceCompute.compute:97-104) per channel in [0, 1] and the bounce rays per pixel; zero = off.  Not
+    // supported together with shadow rays, lodPixels or gpus > 1.
+    public Vector3 specular;
+    [Range(0,7)] public int maxBounces;
+    Vector3 _specularSet;
+    int _maxBouncesSet = 0;
     public enum ShadowForm { Fused = 0, TilePass = 1, CompactedList = 2 }
     public ShadowForm shadowForm = ShadowForm.Fused;
 
@@ -296,6 +311,11 @@ public class RaytracingMasterNative : MonoBehaviour {
         SvoNative.Check(SvoNative.svo_set_lod(_ctx, lodPixels * 2f * Mathf.Abs(_camera.projectionMatrix.inverse[1, 1]) / h, 0f),
                         "svo_set_lod");
         if (lodPixels != _lodPixelsSet) { _lodPixelsSet = lodPixels; _currentSample = 0; }   // another image: a fresh accumulation
+        SvoNative.Check(SvoNative.svo_set_reflection(_ctx, new[] { specular.x, specular.y, specular.z }, maxBounces),
+                        "svo_set_reflection");
+        if (specular != _specularSet || maxBounces != _maxBouncesSet) {   // another image as well
+            _specularSet = specular; _maxBouncesSet = maxBounces; _currentSample = 0;
+        }
         // the pipelined path moves 3-byte pixels (RGB24: a quarter fewer bytes over PCIe); `pipelined`
         // is an Inspector field, so a toggle at run time recreates the texture in the other format
         TextureFormat want = pipelined ? TextureFormat.RGB24 : TextureFormat.RGBA32;
