@@ -178,15 +178,21 @@ struct AssembleParams {
 hipError_t launch_order_tiles(const uint16_t *cost, uint32_t *order, int n_tiles, hipStream_t stream,
                               uint32_t *stats = nullptr);
 size_t order_cost_capacity(int n_tiles);
-// The same per XCD strip (xcd_remap 2): order must hold order_strips_entries(n_tiles, seg_cap)
-// entries.  stats (nullable, 16 words, host-visible memory): per XCD x the max [2 x] and the
-// sum [2 x + 1] of its tiles' costs.  seg_cap > 0: each XCD's tiles of cost >= half its
-// heaviest (at most seg_cap of them, heaviest classes first) are listed as SEG_K quarter
-// entries for render_seg_kernel, the lists padded to one length with SEG_EMPTY; a segmented
-// tile's cost is the max of its part_cost entries.  The render grid is then
-// order_strips_grid(n_tiles, seg_cap) workgroups.
+// The same per XCD strip (xcd_remap 2), six classes: order must hold
+// order_strips_entries(n_tiles, seg_cap, seg_kmax_of(seg_kpack)) entries.  stats (nullable, 16
+// words, host-visible memory): per XCD x the max [2 x] and the sum [2 x + 1] of its tiles' costs.
 // seg_kpack: the K of cost class c (>= 7/8, 3/4, 1/2, 1/4, 1/8 of the XCD's max, rest) in bits
-// 4 c .. 4 c + 3: 0 = not segmented, 4 or 8.
+// 4 c .. 4 c + 3: 0 = not segmented, 4 or 8 (anything else: hipErrorInvalidValue).
+// seg_cap > 0: walking an XCD's classes heaviest first, the tiles of every class with K > 1 are
+// segmented until seg_cap of them are (which tiles of the class the cap cuts off is not defined).
+// Class c's block of the XCD's list holds its segmented tiles first, K consecutive entries
+// t | (code0 + q) << 28 each (q = 0 .. K - 1; code0 = 1 for K = 4, 5 for K = 8), then its other
+// tiles as plain entries; the lists are padded to one length, n_tiles / 8 + (kmax - 1) seg_cap,
+// with SEG_EMPTY.  XCD x's entry j is order[8 j + x]; behind the lists come 4 zero words and per
+// XCD the ends (in j) of the classes 2 .. 5.  A tile whose cost word has SEG_COST_FLAG takes the
+// max of its first 4 part_cost entries (of all 8 when word & 15 == 8) as its cost, if part_cost
+// is given.  The render grid is then order_strips_grid(n_tiles, seg_cap, kmax) workgroups, which
+// must stay below 2^28, and n_tiles must be a multiple of tiles_x (else hipErrorInvalidValue).
 hipError_t launch_order_strips(const uint16_t *cost, uint32_t *order, int n_tiles, int tiles_x, hipStream_t stream,
                                uint32_t *stats = nullptr, int seg_cap = 0, const uint16_t *part_cost = nullptr,
                                int seg_kpack = 0, int spread = 0);

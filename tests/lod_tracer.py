@@ -52,16 +52,13 @@ def _popcount7(x):
     return sum((x >> k) & 1 for k in range(7))
 
 
-def trace(svo, origins, dirs, mode=0, ray_size_coef=0.0, ray_size_bias=0.0):
-    lo, first = svo.masks_and_first()
-    lo = lo.astype(np.int64)
-    first = first.astype(np.int64)
-    o = np.asarray(origins, F32).reshape(-1, 3)
-    d = np.asarray(dirs, F32).reshape(-1, 3)
+def ray_setup(o, d):
+    """The ray setup (:15-43) of n rays, origins o and directions d [n, 3] float32, one IEEE rounding
+    per operation: (org, coef, bias, octant, t_min, t_max) -- the SVO-space origin, the t
+    coefficients and biases per axis (lists of three [n] arrays), the octant mask and the cube's
+    entry (clamped at 0) and exit.  Shared with tests/placement_model.py (the query keys)."""
     n = len(o)
-    coef_l, bias_l = F32(ray_size_coef), F32(ray_size_bias)
-    half_c, two, three, zero = F32(0.5), F32(2.0), F32(3.0), F32(0.0)
-
+    two, three, zero = F32(2.0), F32(3.0), F32(0.0)
     with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
         # :15-19
         org = [o[:, k] * F32(1.0 / 32.0) + F32(1.5) for k in range(3)]
@@ -76,8 +73,23 @@ def trace(svo, origins, dirs, mode=0, ray_size_coef=0.0, ray_size_bias=0.0):
         # :40-43 (HLSL min / max: a NaN operand gives the other one)
         t_min = np.fmax(np.fmax(two * coef[0] - bias[0], two * coef[1] - bias[1]), two * coef[2] - bias[2])
         t_max = np.fmin(np.fmin(coef[0] - bias[0], coef[1] - bias[1]), coef[2] - bias[2])
-        h = t_max.copy()
         t_min = np.fmax(t_min, zero)
+    return org, coef, bias, octant, t_min, t_max
+
+
+def trace(svo, origins, dirs, mode=0, ray_size_coef=0.0, ray_size_bias=0.0):
+    lo, first = svo.masks_and_first()
+    lo = lo.astype(np.int64)
+    first = first.astype(np.int64)
+    o = np.asarray(origins, F32).reshape(-1, 3)
+    d = np.asarray(dirs, F32).reshape(-1, 3)
+    n = len(o)
+    coef_l, bias_l = F32(ray_size_coef), F32(ray_size_bias)
+    half_c, two, three, zero = F32(0.5), F32(2.0), F32(3.0), F32(0.0)
+
+    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+        org, coef, bias, octant, t_min, t_max = ray_setup(o, d)
+        h = t_max.copy()
         # :46-54
         parent = np.zeros(n, np.int64)
         idx = np.zeros(n, np.int32)
