@@ -564,6 +564,66 @@ int svo_bounce_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t f
 int svo_set_reflection(svo_ctx *ctx, const float specular[3], int max_bounces);   /* NULL / 0 = off (default) */
 int svo_get_reflection(svo_ctx *ctx, float specular[3], int *max_bounces);
 
+/* Skybox (opt-in; none by default, and with none every byte is what it was).
+ * ~ RayTracingShader.SetTexture(0, "_SkyboxTexture", SkyboxTexture) (RaytracingMaster.cs:6,28): Shade's miss
+ * branch samples an equirectangular panorama at (phi, theta) = (atan2(d.x, -d.z) / -PI * 0.5, acos(d.y) / -PI)
+ * (RaytraceCompute.compute:119-125).  Without a texture a miss gets the procedural gradient.
+ *
+ * The sky rule: direction d = (x, y, z), used as given (NOT assumed unit), to RGB.  Every operation is one
+ * IEEE f32 rounding, no fma; only + - * /, sqrt, floor, compares and selects (csrc/svo_sky.h; numpy: sky.py):
+ *  1. invalid: a non-finite component, or x = y = z = 0: the colour is (0, 0, 0).  Otherwise d is divided by
+ *     max(|x|, |y|, |z|).
+ *  2. angles: polar = atan2f32(sqrt(x x + z z), y) in [0, PI]; azim = atan2f32(x, -z).  atan2f32 is the rule's
+ *     own (INTEGRATION.md "Skybox" spells it out); atan2f32(+-0, positive) = +-0, atan2f32(0, 0) = +0.  For a unit
+ *     direction polar is the reference's acos(d.y): a restatement, mathematically identical, in other f32
+ *     operations (no normalisation needed, well conditioned at the poles).
+ *  3. theta = polar / -PI, phi = azim / -PI * 0.5f, PI = 3.14159265f; the sample point is (phi, theta).
+ *  4. wrap: u = phi - floor(phi), a result of 1 becomes 0.  v: the same on theta (repeat, Unity's default
+ *     wrapMode), or min(max(theta + 1, 0), 1) with SVO_SKY_CLAMP_V (row indices then clamp to [0, H - 1]).
+ *  5. nearest: i = min((int)floor(u W), W - 1), j = min((int)floor(v H), H - 1).
+ *  6. SVO_SKY_BILINEAR: x = u W - 0.5, i0 = floor(x), fx = x - i0, columns i0 and i0 + 1 wrapped mod W; rows
+ *     likewise, wrapped mod H or clamped; c = (t00 (1 - fx) + t10 fx) (1 - fy) + (t01 (1 - fx) + t11 fx) fy
+ *     per channel, in that order.
+ *  7. rows: texel (i, j) is rgba[4 (j W + i)], row 0 is v = 0 -- Unity's raw texel order (GetPixels /
+ *     GetPixelData: bottom row first).  The horizon is v = 0.5, "up" is towards the last row; straight up
+ *     itself is theta = 0: row 0 with repeat (as in the reference), the last row with clamp.
+ * (u, v) is within 1.0e-7 of the exact value (measured), 1/1200 texel at the largest size.
+ *
+ * svo_set_skybox: rgba is a HOST array of width x height x 4 floats (a Unity Color[]; alpha is ignored),
+ * copied before the call returns; the texels live on the context's device.  NULL: back to the gradient
+ * (width, height ignored).  Waits for every stream that may still read the previous texture.  Not a
+ * svo_config field: svo_config never changes results.  Leaves the dispatch-order state, tile costs, beam
+ * starts and view-change detection alone.  SVO_ERR_ARG, checked before any device is touched: a NULL
+ * context, unknown flag bits, and with a non-NULL rgba a non-positive size, a size above 8192, or a colour
+ * component (alpha excepted) that is negative or not finite.  SVO_ERR_STATE: a non-NULL rgba on a
+ * multi-device context.  svo_get_skybox: 0 x 0 = none; every pointer may be NULL.
+ *
+ * Renders: with a texture set, every pixel whose hit-mask bit is clear (a miss, also one whose record
+ * carries the iteration-cap or stack-overflow flag) gets the rule's colour of its camera ray's direction
+ * (alpha 1), in rgba, rgba8 and rgb8 (and through them a progressive accumulation).  Hit pixels and every
+ * other output are untouched.  It is a pass behind the primary launch, which takes exactly the path it takes
+ * without a texture (it additionally writes its tile hit masks to context-owned scratch when the caller
+ * passed no hitmask).  With svo_set_reflection, bounce rays that miss take the rule on their traced
+ * direction.  Served: svo_render, svo_render_device, svo_render_frame (any band, layout and stream) and
+ * svo_render_progressive(_async); it combines with SVO_OPT_SHADOW_RAYS, LOD and reflection without new
+ * rules.  svo_count_fetches and svo_beam_starts are unaffected, and so is svo_assemble_frame: compact and
+ * sparse parts get the display side's gradient on misses, so a one-process-per-GPU split with a skybox
+ * sends dense RGB8 / RGBA8 parts (band renders fill them correctly).  Stated limit: svo_render_samples
+ * with a texture set returns SVO_ERR_STATE before anything is enqueued.
+ *
+ * svo_sample_sky: the rule for caller-supplied directions -- the texture if one is set, else the gradient
+ * 0.25 + 0.5 k, 0.35 + 0.55 k, 0.6 + 0.4 k with k = 0.5 y + 0.5 of the direction's y as given (an invalid
+ * direction is black here too) -- the shading a ray-query user lacks for rays that miss.  d_dirs: n float4
+ * (w ignored), d_rgba: n float4 (alpha 1), device pointers on the context's device (a multi-device
+ * context: devices[0]), 16-byte aligned; d_rgba may be d_dirs.  Writes nothing past n entries; n == 0:
+ * SVO_OK, nothing launched; NULL pointers, n > 2^31 - 1: SVO_ERR_ARG.  Asynchronous on `stream` (NULL: the
+ * context's own); the host form blocks. */
+enum { SVO_SKY_BILINEAR = 1, SVO_SKY_CLAMP_V = 2 };
+int svo_set_skybox(svo_ctx *ctx, const float *rgba, int width, int height, uint32_t flags);   /* NULL = procedural (default) */
+int svo_get_skybox(svo_ctx *ctx, int *width, int *height, uint32_t *flags);                   /* 0 x 0: none */
+int svo_sample_sky(svo_ctx *ctx, const float *d_dirs, size_t n, float *d_rgba, void *stream);
+int svo_sample_sky_host(svo_ctx *ctx, const float *dirs, size_t n, float *rgba);
+
 /* Information about the uploaded pool. */
 int svo_get_info(svo_ctx *ctx, size_t *n_nodes, int *max_depth, int *device);
 

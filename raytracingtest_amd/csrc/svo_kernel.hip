@@ -1753,10 +1753,13 @@ __global__ __launch_bounds__(256) void bounce_rays_kernel(const QueryRay *rays, 
 // when the wave's ballot of `alive` is non-zero (its mask comes from exec and must not be empty), and
 // the loop is left on that ballot alone.  Hit pixels' colours are overwritten with plain stores; the
 // records, keys, positions and masks stay the primary ray's.
-template <int MODE, bool GUARD, bool FA>
-__global__ __launch_bounds__(TILE) void reflect_list_kernel(LaunchParams p, const uint32_t *__restrict__ list,
-                                                            const uint32_t *__restrict__ count, float sr, float sg,
-                                                            float sb, int max_bounces) {
+// SKY (svo_set_skybox): a bounce ray that misses takes the sky rule (svo_sky.h) on its traced direction
+// instead of the gradient -- reflect_list_sky_kernel; the instantiations without it never see `tex`.
+// p by value: through a reference the kernels without SKY took 6 more SGPRs than before the body was shared.
+template <int MODE, bool GUARD, bool FA, bool SKY>
+__device__ __forceinline__ void reflect_list_body(const LaunchParams p, const uint32_t *__restrict__ list,
+                                                  const uint32_t *__restrict__ count, float sr, float sg, float sb,
+                                                  int max_bounces, const svo_sky::Texture &tex) {
     extern __shared__ uint2 stk_base[];
     const int lane = (int)threadIdx.x;
     const uint32_t k = blockIdx.x * TILE + (uint32_t)lane;
@@ -1824,6 +1827,8 @@ __global__ __launch_bounds__(TILE) void reflect_list_kernel(LaunchParams p, cons
                 Record h;
                 hit_position(r, o, d, h);
                 key = h.key;
+            } else if (SKY) {
+                svo_sky::sample(tex, d, col);
             } else {
                 sky(r.dir_y, col);
             }
@@ -1845,6 +1850,69 @@ __global__ __launch_bounds__(TILE) void reflect_list_kernel(LaunchParams p, cons
             dst[2] = (uint8_t)(w >> 16);
         }
     }
+}
+
+template <int MODE, bool GUARD, bool FA>
+__global__ __launch_bounds__(TILE) void reflect_list_kernel(LaunchParams p, const uint32_t *__restrict__ list,
+                                                            const uint32_t *__restrict__ count, float sr, float sg,
+                                                            float sb, int max_bounces) {
+    reflect_list_body<MODE, GUARD, FA, false>(p, list, count, sr, sg, sb, max_bounces, svo_sky::Texture{});
+}
+
+template <int MODE, bool GUARD, bool FA>
+__global__ __launch_bounds__(TILE) void reflect_list_sky_kernel(LaunchParams p, const uint32_t *__restrict__ list,
+                                                                const uint32_t *__restrict__ count, float sr, float sg,
+                                                                float sb, int max_bounces, svo_sky::Texture tex) {
+    reflect_list_body<MODE, GUARD, FA, true>(p, list, count, sr, sg, sb, max_bounces, tex);
+}
+
+// ------------------------------------------------------------------ skybox
+// svo_set_skybox: the sky pass behind the primary launch.  One wave64 per 8x8 tile of the
+// launch's rows, in plain tile order (the pass has no heavy tiles to put first).  The tile's hit mask is
+// one wave-uniform word; a tile with no miss inside the frame returns at once.  A miss lane rebuilds its
+// camera ray with the render's own camera_ray -- the direction the primary kernel traced, bit for bit --
+// evaluates the rule (svo_sky.h) and stores the colour at the render's own addresses.  Hit pixels and every
+// non-colour output are not touched; a miss record that carries the iteration-cap or stack-overflow flag
+// has a clear mask bit and gets the sky like any other miss, as in the primary kernel.
+__global__ __launch_bounds__(TILE) void sky_fill_kernel(LaunchParams p, svo_sky::Texture tex,
+                                                        const unsigned long long *__restrict__ masks, int tiles_x) {
+    const int lane = (int)threadIdx.x;
+    const int t = (int)blockIdx.x;
+    const unsigned long long hit = masks[t];
+    const int bx = t % tiles_x, by = t / tiles_x;
+    const int x = bx * 8 + (lane & 7);
+    const int lr = by * 8 + (lane >> 3);
+    const bool miss = x < p.width && lr < p.local_rows && ((hit >> lane) & 1ull) == 0ull;
+    if (LM_OF(miss) == 0) return;   // the whole wave
+    if (!miss) return;
+    const int gy = global_row(p, lr);
+    const size_t i = out_index(p, lr, gy, x);
+    float org[3], dir[3], rgb[3];
+    camera_ray(p.cam, p.width, p.height, x, gy, org, dir);
+    svo_sky::sample(tex, dir, rgb);
+    if (p.out.rgba) p.out.rgba[i] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
+    if (p.out.rgba8 || p.out.rgb8) {
+        const uint32_t w = pack_rgba8(rgb[0], rgb[1], rgb[2]);
+        if (p.out.rgba8) p.out.rgba8[i] = w;
+        if (p.out.rgb8) {
+            uint8_t *dst = p.out.rgb8 + 3 * i;
+            dst[0] = (uint8_t)w;
+            dst[1] = (uint8_t)(w >> 8);
+            dst[2] = (uint8_t)(w >> 16);
+        }
+    }
+}
+
+// svo_sample_sky: one thread per direction; a thread reads its own entry before it writes its own slot, so
+// out may be dirs (no __restrict__ on either).
+__global__ __launch_bounds__(256) void sample_sky_kernel(svo_sky::Texture tex, const float4 *dirs, uint32_t n, float4 *out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const float4 d4 = dirs[i];
+    const float d[3] = {d4.x, d4.y, d4.z};
+    float rgb[3];
+    svo_sky::sample(tex, d, rgb);
+    out[i] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
 }
 
 // ---------------------------------------------------------- frame assembly
@@ -2924,7 +2992,15 @@ static hipError_t launch_reflect_mode(const LaunchParams &q, const uint32_t *lis
     const dim3 grid((unsigned)(((size_t)q.width * (size_t)q.local_rows + TILE - 1) / TILE)), block(TILE);
     const float sr = ra.specular[0], sg = ra.specular[1], sb = ra.specular[2];
     // guarded pools and fetch_all select the loop as shadow_list_kernel does
-    if (q.guard)
+    if (ra.sky.texels) {
+        if (q.guard)
+            hipLaunchKernelGGL((reflect_list_sky_kernel<MODE, true, false>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces, ra.sky);
+        else if (q.fetch_all)
+            hipLaunchKernelGGL((reflect_list_sky_kernel<MODE, false, true>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces, ra.sky);
+        else
+            hipLaunchKernelGGL((reflect_list_sky_kernel<MODE, false, false>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces, ra.sky);
+    }
+    else if (q.guard)
         hipLaunchKernelGGL((reflect_list_kernel<MODE, true, false>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces);
     else if (q.fetch_all)
         hipLaunchKernelGGL((reflect_list_kernel<MODE, false, true>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces);
@@ -2947,6 +3023,24 @@ hipError_t launch_reflect(const LaunchParams &p, const ReflectArgs &ra, int stac
     LaunchParams q = p;
     q.out.hitmask = nullptr;
     return stack_mode == 0 ? launch_reflect_mode<0>(q, list, cnt, ra, stream) : launch_reflect_mode<1>(q, list, cnt, ra, stream);
+}
+
+hipError_t launch_sky_fill(const LaunchParams &p, const svo_sky::Texture &sky, const unsigned long long *masks,
+                           hipStream_t stream) {
+    if (!sky.texels || sky.width <= 0 || sky.height <= 0 || !masks || p.width <= 0 || p.local_rows <= 0)
+        return hipErrorInvalidValue;
+    if (!p.out.rgba && !p.out.rgba8 && !p.out.rgb8) return hipSuccess;
+    const int bx = (p.width + 7) / 8, by = (p.local_rows + 7) / 8;
+    hipLaunchKernelGGL(sky_fill_kernel, dim3((unsigned)(bx * by)), dim3(TILE), 0, stream, p, sky, masks, bx);
+    return hipGetLastError();
+}
+
+hipError_t launch_sample_sky(const svo_sky::Texture &sky, const float4 *dirs, uint32_t n, float4 *out,
+                             hipStream_t stream) {
+    if (!dirs || !out || (sky.texels && (sky.width <= 0 || sky.height <= 0))) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(sample_sky_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, sky, dirs, n, out);
+    return hipGetLastError();
 }
 
 }  // namespace svo

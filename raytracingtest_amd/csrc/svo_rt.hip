@@ -266,6 +266,10 @@ struct svo_ctx {
     int max_bounces = 0;
     unsigned long long *d_refl_voxel = nullptr;
     size_t refl_voxel_cap = 0;
+    // skybox (svo_set_skybox; texels null: the procedural gradient -- DESIGN.md 3.2d): the texture on this
+    // device, one float4 per texel; the sky pass reads the tile hit masks from the caller's array or from
+    // the head of d_shadow_list (the shadow forms' and the reflection pass's scratch)
+    svo_sky::Texture sky{nullptr, 0, 0, 0u};
     // diagnostics (the library's only environment switches, read once at svo_create):
     // SVO_DEBUG bit 0 the loop-form / class-table decision trace, bit 1 the order each launch
     // takes; SVO_WAVE_LOG=<file> the per-wave record; SVO_BEAM_DIAG the splat's timing variants
@@ -1182,8 +1186,34 @@ int reflect_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsign
     ra.scratch = ctx->d_shadow_list;
     for (int k = 0; k < 3; ++k) ra.specular[k] = ctx->specular[k];
     ra.max_bounces = ctx->max_bounces;
+    ra.sky = ctx->sky;   // texels null: bounce rays that miss keep the gradient
     const hipError_t e = svo::launch_reflect(p, ra, L.stack_mode, L.s);
     if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("reflection launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
+// The sky pass's input: the launch's tile hit masks.  A caller's own masks are read
+// where they are; so are shadow form 2's and the reflection pass's, which already made the primary launch
+// write them to the head of the shared scratch (their list builds leave the head alone).  Otherwise the
+// primary launch writes them there for this pass.
+int sky_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
+    if (p.out.hitmask) return SVO_OK;
+    const size_t need = svo::shadow_list_bytes(p.width, p.local_rows);
+    if (ctx->shadow_list_cap < need) {
+        HIP_TRY(hipDeviceSynchronize());   // an earlier launch may still read the old list
+        const int rc = regrow(&ctx->d_shadow_list, &ctx->shadow_list_cap, need, need);
+        if (rc) return rc;
+    }
+    const int rc = order_scratch(ctx, L.s);
+    if (rc) return rc;
+    p.out.hitmask = reinterpret_cast<unsigned long long *>(ctx->d_shadow_list);
+    return SVO_OK;
+}
+
+// Behind the primary launch (and the reflection pass): every miss pixel's colour from the texture.
+int sky_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p) {
+    const hipError_t e = svo::launch_sky_fill(p, ctx->sky, p.out.hitmask, L.s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("sky launch: ") + hipGetErrorString(e));
     return SVO_OK;
 }
 
@@ -1636,6 +1666,10 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     if (refl_on && (ctx->options & SVO_OPT_SHADOW_RAYS))
         return fail(SVO_ERR_STATE, "shadow rays with reflection are not supported");
     if (refl_on && lod) return fail(SVO_ERR_STATE, "reflection with LOD is not supported");
+    // skybox (svo_set_skybox): a pass behind the primary rays (and the bounces) that recolours the misses;
+    // svo_render_samples blends in its own launch's epilogue, before any pass could run
+    const bool sky_on = ctx->sky.texels && !out.fetches && !out.starts;
+    if (sky_on && sa) return fail(SVO_ERR_STATE, "svo_render_samples with a skybox texture is not supported");
     LaunchPlan L;
     L.stack_mode = stack_mode;
     int rc = check_band(band, height, &L.b);
@@ -1663,6 +1697,12 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     unsigned long long *caller_mask = nullptr;
     if (reflect) {
         rc = reflect_scratch(ctx, L, p, &caller_mask);
+        if (rc) return rc;
+    }
+    // the same for the sky pass: only a launch that writes a colour has one
+    const bool sky = sky_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
+    if (sky) {
+        rc = sky_scratch(ctx, L, p);
         if (rc) return rc;
     }
     p.prio = ctx->prio;
@@ -1693,6 +1733,10 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     if (rc) return rc;
     if (reflect) {
         rc = reflect_pass(ctx, L, p, caller_mask);
+        if (rc) return rc;
+    }
+    if (sky) {
+        rc = sky_pass(ctx, L, p);
         if (rc) return rc;
     }
     return finish_launch(ctx, L, p);
@@ -1950,6 +1994,7 @@ int destroy_single(svo_ctx *ctx) {
     if (ctx->d_stage) hipFree(ctx->d_stage);
     if (ctx->d_shadow_list) hipFree(ctx->d_shadow_list);
     if (ctx->d_refl_voxel) hipFree(ctx->d_refl_voxel);
+    if (ctx->sky.texels) hipFree(const_cast<svo_sky::Texel *>(ctx->sky.texels));
     if (ctx->d_out_hits) hipFree(ctx->d_out_hits);
     if (ctx->d_out_rgba) hipFree(ctx->d_out_rgba);
     if (ctx->d_accum) hipFree(ctx->d_accum);
@@ -2233,6 +2278,21 @@ int bounce_device(const void *d_rays, size_t n, uint32_t flags, const void *d_hi
                                                  reinterpret_cast<const unsigned long long *>(d_voxel),
                                                  reinterpret_cast<svo::QueryRay *>(d_rays_out), s);
     if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("bounce launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
+int check_sky_args(svo_ctx *ctx, const float *dirs, size_t n, const float *rgba) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!dirs) return fail(SVO_ERR_ARG, "null direction list");
+    if (!rgba) return fail(SVO_ERR_ARG, "null colour output");
+    if (n > 0x7FFFFFFFu) return fail(SVO_ERR_ARG, "more than 2^31 - 1 directions");
+    return SVO_OK;
+}
+
+int sample_sky_device(svo_ctx *c, const void *d_dirs, size_t n, void *d_rgba, hipStream_t s) {
+    const hipError_t e = svo::launch_sample_sky(c->sky, reinterpret_cast<const float4 *>(d_dirs), (uint32_t)n,
+                                                reinterpret_cast<float4 *>(d_rgba), s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("sky sample launch: ") + hipGetErrorString(e));
     return SVO_OK;
 }
 
@@ -2686,6 +2746,91 @@ int svo_get_reflection(svo_ctx *ctx, float specular[3], int *max_bounces) {
     for (int k = 0; k < 3 && specular; ++k) specular[k] = ctx->specular[k];
     if (max_bounces) *max_bounces = ctx->max_bounces;
     return SVO_OK;
+}
+
+int svo_set_skybox(svo_ctx *ctx, const float *rgba, int width, int height, uint32_t flags) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (flags & ~(uint32_t)(SVO_SKY_BILINEAR | SVO_SKY_CLAMP_V)) return fail(SVO_ERR_ARG, "unknown skybox flag bits");
+    if (rgba) {
+        if (width <= 0 || height <= 0) return fail(SVO_ERR_ARG, "skybox width/height must be positive");
+        if (width > svo_sky::MAX_DIM || height > svo_sky::MAX_DIM)
+            return fail(SVO_ERR_ARG, "skybox width/height must not exceed " + std::to_string(svo_sky::MAX_DIM));
+        const size_t n = (size_t)width * (size_t)height;
+        for (size_t i = 0; i < n; ++i)
+            for (int k = 0; k < 3; ++k) {   // alpha is ignored
+                const float c = rgba[4 * i + k];
+                if (!(c >= 0.0f && c <= std::numeric_limits<float>::max()))
+                    return fail(SVO_ERR_ARG, "skybox colour components must be finite and non-negative");
+            }
+        if (is_multi(ctx)) return fail(SVO_ERR_STATE, "a skybox texture on a multi-device context is not supported");
+    }
+    if (!rgba && !ctx->sky.texels) return SVO_OK;   // nothing set, nothing to release (a multi-device context too)
+    HIP_TRY(hipSetDevice(ctx->device));
+    // renders, queries and svo_sample_sky on any stream may still read the previous texture
+    HIP_TRY(hipDeviceSynchronize());
+    if (ctx->sky.texels) hipFree(const_cast<svo_sky::Texel *>(ctx->sky.texels));
+    ctx->sky = svo_sky::Texture{nullptr, 0, 0, 0u};
+    if (!rgba) return SVO_OK;
+    const size_t bytes = (size_t)width * (size_t)height * sizeof(svo_sky::Texel);
+    svo_sky::Texel *d = nullptr;
+    HIP_TRY(hipMalloc(&d, bytes));
+    const hipError_t e = hipMemcpy(d, rgba, bytes, hipMemcpyHostToDevice);   // blocking: SetData semantics
+    if (e != hipSuccess) {
+        hipFree(d);
+        return fail(SVO_ERR_HIP, std::string("skybox upload: ") + hipGetErrorString(e));
+    }
+    ctx->sky = svo_sky::Texture{d, width, height, flags};
+    return SVO_OK;
+}
+
+int svo_get_skybox(svo_ctx *ctx, int *width, int *height, uint32_t *flags) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (width) *width = ctx->sky.width;
+    if (height) *height = ctx->sky.height;
+    if (flags) *flags = ctx->sky.flags;
+    return SVO_OK;
+}
+
+int svo_sample_sky(svo_ctx *ctx, const float *d_dirs, size_t n, float *d_rgba, void *stream) {
+    int rc = check_sky_args(ctx, d_dirs, n, d_rgba);
+    if (rc) return rc;
+    if (((uintptr_t)d_dirs | (uintptr_t)d_rgba) & 15u) return fail(SVO_ERR_ARG, "directions and colours must be 16-byte aligned");
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        return sample_sky_device(c, d_dirs, n, d_rgba, stream ? (hipStream_t)stream : c->stream);
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_sample_sky: ") + e.what());
+    }
+}
+
+int svo_sample_sky_host(svo_ctx *ctx, const float *dirs, size_t n, float *rgba) {
+    int rc = check_sky_args(ctx, dirs, n, rgba);
+    if (rc) return rc;
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        // staged in the ray queries' scratch: the directions, 16 bytes each, sampled in place
+        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, 16 * n);
+        if (rc) return rc;
+        rc = order_query_scratch(c, c->stream);
+        if (rc) return rc;
+        char *base = static_cast<char *>(c->q_host);
+        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
+            hipStream_t s;
+            ~Drain() { hipStreamSynchronize(s); }
+        } drain{c->stream};
+        HIP_TRY(hipMemcpyAsync(base, dirs, 16 * n, hipMemcpyHostToDevice, c->stream));
+        rc = sample_sky_device(c, base, n, base, c->stream);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(rgba, base, 16 * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SVO_OK;
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_sample_sky_host: ") + e.what());
+    }
 }
 
 int svo_get_lod(svo_ctx *ctx, float *ray_size_coef, float *ray_size_bias) {

@@ -13,6 +13,8 @@
 
 #include <algorithm>
 
+#include "svo_sky.h"
+
 namespace svo {
 
 constexpr int S_MAX = 23;          // NVIDIASVO.compute:2
@@ -269,8 +271,21 @@ struct ReflectArgs {
     void *scratch;
     float specular[3];
     int max_bounces;          // 1 .. 7
+    svo_sky::Texture sky;     // texels non-null: a bounce ray that misses takes the sky rule on its traced direction
 };
 hipError_t launch_reflect(const LaunchParams &p, const ReflectArgs &ra, int stack_mode, hipStream_t stream);
+
+// Skybox (svo_set_skybox; svo_sky.h is the rule).
+// Sky pass behind a render launch's primary rays (sky_fill_kernel): one wave64 per 8x8 tile of the launch's
+// rows reads the tile's hit mask (masks: svo_frame.hitmask's layout, band-local tiles) as one wave-uniform
+// word and gives every in-frame pixel whose bit is clear the rule's colour of its camera ray's direction,
+// in the colour outputs among out.rgba / rgba8 / rgb8.  p: the launch's own parameters.
+hipError_t launch_sky_fill(const LaunchParams &p, const svo_sky::Texture &sky, const unsigned long long *masks,
+                           hipStream_t stream);
+// svo_sample_sky: out[i] = {the rule on dirs[i].xyz, 1} (texels null: the gradient).  A flat launch, one
+// thread per direction; out may be dirs.
+hipError_t launch_sample_sky(const svo_sky::Texture &sky, const float4 *dirs, uint32_t n, float4 *out,
+                             hipStream_t stream);
 
 // Ray queries (svo_trace_rays; svo_kernel.hip query_rays_kernel): one wave64 traces 64
 // consecutive entries of a flat list of world-space rays with the primary rays' lean loop.

@@ -185,6 +185,52 @@ class RaytracingMaster:
         check(_lib.lib().svo_get_reflection(self._ctx, s, ctypes.byref(n)), "svo_get_reflection")
         return (s[0], s[1], s[2]), n.value
 
+    def SetSkybox(self, texels, bilinear=True, clamp_v=False):
+        """~ RayTracingShader.SetTexture(0, "_SkyboxTexture", SkyboxTexture) (RaytracingMaster.cs:28;
+        svo_set_skybox): an equirectangular panorama for the rays that leave the scene.  texels: H x W x 4
+        (or x 3) floats, finite and non-negative, row 0 = v = 0 (Unity's GetPixels order, bottom row
+        first), alpha ignored; None: back to the procedural gradient (the default).  sky.sample_sky is the
+        rule.  Only the miss pixels' colours (and bounce rays that miss) change."""
+        before = self.GetSkybox()
+        if texels is None:
+            check(_lib.lib().svo_set_skybox(self._ctx, None, 0, 0, 0), "svo_set_skybox")
+        else:
+            t = np.asarray(texels, np.float32)
+            if t.ndim != 3 or t.shape[2] not in (3, 4):
+                raise ValueError(f"skybox texels must be H x W x 3 or H x W x 4, got {t.shape}")
+            if t.shape[2] == 3:
+                t = np.concatenate([t, np.ones(t.shape[:2] + (1,), np.float32)], axis=2)
+            t = np.ascontiguousarray(t)
+            flags = (_lib.SKY_BILINEAR if bilinear else 0) | (_lib.SKY_CLAMP_V if clamp_v else 0)
+            check(_lib.lib().svo_set_skybox(self._ctx, t.ctypes.data, t.shape[1], t.shape[0], flags), "svo_set_skybox")
+        if texels is not None or before != (0, 0, 0):   # another image: the accumulation restarts
+            self.currentSample = 0
+
+    def GetSkybox(self):
+        """(width, height, flags) of the context's skybox texture (svo_get_skybox); (0, 0, 0): none."""
+        w, h, fl = ctypes.c_int(), ctypes.c_int(), ctypes.c_uint32()
+        check(_lib.lib().svo_get_skybox(self._ctx, ctypes.byref(w), ctypes.byref(h), ctypes.byref(fl)), "svo_get_skybox")
+        return w.value, h.value, fl.value
+
+    def SampleSky(self, dirs):
+        """The sky colour of n directions (svo_sample_sky_host; sky.sample_sky is its numpy statement):
+        the texture if one is set, else the gradient.  dirs: n x 3 (or n x 4, w ignored), used as given,
+        not normalised.  Returns n x 4 f32 (alpha 1)."""
+        d = np.asarray(dirs, np.float32)
+        d = d.reshape(-1, d.shape[-1] if d.ndim > 1 else 3)
+        if d.shape[1] not in (3, 4):
+            raise ValueError(f"directions must be n x 3 or n x 4, got {d.shape}")
+        d4 = np.zeros((len(d), 4), np.float32)
+        d4[:, :d.shape[1]] = d
+        out = np.zeros((len(d), 4), np.float32)
+        check(_lib.lib().svo_sample_sky_host(self._ctx, d4.ctypes.data, len(d4), out.ctypes.data), "svo_sample_sky_host")
+        return out
+
+    def sample_sky_device(self, dirs_ptr, n, rgba_ptr, stream=None):
+        """Asynchronous svo_sample_sky on device buffers: dirs_ptr = n float4 (w ignored), rgba_ptr = n
+        float4 (alpha 1), 16-byte aligned; rgba_ptr may be dirs_ptr."""
+        check(_lib.lib().svo_sample_sky(self._ctx, dirs_ptr, int(n), rgba_ptr, stream), "svo_sample_sky")
+
     def set_count_beam(self, enable=True):
         """SVO_OPT_COUNT_BEAM: count_fetches_device counts the fetches of the walk the render runs
         (from the beam start) instead of the reference's walk from the cube entry."""

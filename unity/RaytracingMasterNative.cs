@@ -98,6 +98,12 @@ public static class SvoNative {
                                                                    [Out] SvoRay[] raysOut);
     [DllImport(Lib)] public static extern int svo_set_reflection(IntPtr ctx, [In] float[] specular, int maxBounces);
     [DllImport(Lib)] public static extern int svo_get_reflection(IntPtr ctx, [Out] float[] specular, out int maxBounces);
+    // Skybox (svo_rt.h): the reference's _SkyboxTexture for rays that leave the scene, and its rule for ray queries
+    public const uint SkyBilinear = 1, SkyClampV = 2;
+    [DllImport(Lib)] public static extern int svo_set_skybox(IntPtr ctx, [In] Color[] rgba, int width, int height, uint flags);
+    [DllImport(Lib)] public static extern int svo_get_skybox(IntPtr ctx, out int width, out int height, out uint flags);
+    [DllImport(Lib)] public static extern int svo_sample_sky(IntPtr ctx, IntPtr dDirs, UIntPtr n, IntPtr dRgba, IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_sample_sky_host(IntPtr ctx, [In] Vector4[] dirs, UIntPtr n, [Out] Color[] rgba);
 
     [StructLayout(LayoutKind.Sequential)]
     public struct SvobResult {   // == svob_result
@@ -159,6 +165,12 @@ public class RaytracingMasterNative : MonoBehaviour {
     [Range(0,7)] public int maxBounces;
     Vector3 _specularSet;
     int _maxBouncesSet = 0;
+    // Skybox (svo_set_skybox; it changes the image): the reference's SkyboxTexture (RaytracingMaster.cs:6), an
+    // equirectangular panorama (readable, at most 8192 x 8192), uploaded once when the context is created as the
+    // reference binds it once in Awake (:28).  None: the procedural gradient.  Not supported with gpus > 1.
+    public Texture2D SkyboxTexture;
+    public bool skyboxBilinear = true;           // the texture's filterMode Bilinear (false: Point)
+    public bool skyboxClampV;                    // wrapModeV Clamp (false: Repeat, Unity's import default)
     public enum ShadowForm { Fused = 0, TilePass = 1, CompactedList = 2 }
     public ShadowForm shadowForm = ShadowForm.Fused;
 
@@ -236,6 +248,16 @@ public class RaytracingMasterNative : MonoBehaviour {
         }
         _ctx = ctx;
         ApplyConfig();
+        UploadSkybox();
+    }
+
+    // RaytracingMaster.cs:28.  GetPixels returns the texels row by row from the bottom row, which is the plugin's
+    // row 0 = v = 0 (INTEGRATION.md "Skybox": reasoned from the API documentation, not observed).
+    void UploadSkybox() {
+        if (SkyboxTexture == null) return;
+        uint flags = (skyboxBilinear ? SvoNative.SkyBilinear : 0u) | (skyboxClampV ? SvoNative.SkyClampV : 0u);
+        SvoNative.Check(SvoNative.svo_set_skybox(_ctx, SkyboxTexture.GetPixels(), SkyboxTexture.width, SkyboxTexture.height,
+                                                 flags), "svo_set_skybox");
     }
 
     // the Inspector fields into the context's svo_config; the other fields keep the library's values
