@@ -2699,7 +2699,7 @@ hipError_t launch_assemble(const AssembleParams &a, hipStream_t stream) {
 }
 
 // ------------------------------------------------------------- beam splat
-// One thread per box of the pool's splat list (svo_rt.hip build_beam_boxes): the box's Euclidean
+// One thread per box of the pool's splat list (svo_beam.h build_beam_boxes): the box's Euclidean
 // distance from the camera bounds from below the t at which any ray can enter it, so that
 // distance is min-ed into every 8x8 tile whose rays can reach the box -- those whose pixel area
 // (any offset in [0, 1]) meets the box's screen projection.  The projection is the bounding box of

@@ -214,7 +214,7 @@ inline size_t order_strips_entries(int n_tiles, int seg_cap, int kmax = SEG_KMAX
 }
 
 // Beam starts of one launch: every box of the pool's splat list (the nodes at
-// the splat depth and the leaves above it, svo_rt.hip build_beam_boxes) is projected onto the
+// the splat depth and the leaves above it, svo_beam.h build_beam_boxes) is projected onto the
 // screen, and its distance from the camera min-ed into every 8x8 tile its projection touches
 // (a 64x64 super tile or the one global word when it touches more than 32), as the key
 // ~gen << 32 | distance bits: no fill pass, stale entries lose every min (tiles_x * tiles_y +
@@ -230,7 +230,6 @@ struct BeamParams {
     float org[3];          // camera origin in SVO space, bit-identical to the render's
     float minv[9];         // row-major inverse of M: unnormalised ray direction = M (fx, fy, 1), fx, fy
                            // continuous pixel coordinates (pixel x, offset o: fx = x + o)
-    float minv_abs[3];     // sum_k |minv[r][k]| per row r, rounded up: a box's half extents in q-space
     float plane[4][3];     // the view frustum's side planes through the camera, normals pointing in
 };
 hipError_t launch_beam_splat(const BeamParams &b, hipStream_t stream);

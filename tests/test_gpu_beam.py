@@ -362,3 +362,133 @@ def test_held_view_resplat_is_finer_and_exact(torch, oracle_mod, c3_svo, mode):
         finally:
             m.close()
     assert fetches[0] < fetches[-1], fetches
+
+
+def _ray_setup_f32(c2w, inv_proj, w, h, off=(0.5, 0.5)):
+    """camera_ray + setup_ray of svo_kernel.hip in numpy float32, operation by operation (plain IEEE f32, no
+    contraction): the normalised directions and beam_start's margin m = (2 sum |coef| + sum |bias|) 2^-20."""
+    f = np.float32
+    cm = np.asarray(c2w, f).T.reshape(-1)        # column-major, as the kernel indexes it
+    ip = np.asarray(inv_proj, f).T.reshape(-1)
+    x = (np.arange(w * h) % w).astype(f)
+    y = (np.arange(w * h) // w).astype(f)
+    u = (x + f(off[0])) / f(w) * f(2) - f(1)
+    v = (y + f(off[1])) / f(h) * f(2) - f(1)
+
+    def mul4(m, v0, v1, v2, v3):
+        return [((m[r] * v0 + m[4 + r] * v1) + m[8 + r] * v2) + m[12 + r] * v3 for r in range(3)]
+    zero, one = np.zeros_like(u), np.ones_like(u)
+    org = mul4(cm, zero, zero, zero, one)
+    pd = mul4(ip, u, v, zero, one)
+    d = mul4(cm, pd[0], pd[1], pd[2], zero)
+    inv = f(1) / np.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
+    d = [c * inv for c in d]
+    m = None
+    with np.errstate(divide="ignore", invalid="ignore"):
+        coef = [f(1) / -np.abs(c) for c in d]
+        bias = []
+        for k in range(3):
+            o = org[k] * f(1.0 / 32.0) + f(1.5)
+            b = coef[k] * o
+            bias.append(np.where(d[k] > 0, f(3) * coef[k] - b, b))
+        m = (((f(2) * ((np.abs(coef[0]) + np.abs(coef[1])) + np.abs(coef[2])) + np.abs(bias[0])) + np.abs(bias[1])) +
+             np.abs(bias[2])) * f(2.0 ** -20)
+    return np.stack(d, axis=1), m
+
+
+def _two_sided_pools():
+    from raytracingtest_amd.builder import build_from_leaves
+    rng = np.random.default_rng(0x2B)
+    flat = rng.choice(64 ** 3, size=3000, replace=False)
+    xyz = np.stack([flat % 64, flat // 64 % 64, flat // 4096], axis=1)
+    return {"menger4": build_menger(4, 2),
+            "random6": build_from_leaves(6, xyz, np.tile(np.array([0.0, 1.0, 0.0], np.float32), (len(xyz), 1)))}
+
+
+def test_beam_starts_two_sided(torch):
+    """The start every primary ray gets (svo_beam_starts) against the models of tests/beam_model.py, from both
+    sides: the splat list of the pool (splat_list_model), the camera as the host rounds it (beam_camera_model,
+    f32), the envelope [lo_rule, hi_rule] of the tile's bound (splat_model).  The kernel's start is
+    s = fl(fl(d (1 - 2^-16)) - m); d' = (s + m) / (1 - 2^-16) must lie in
+    [lo_rule (1 - 2^-21) - k, hi_rule (1 + 2^-21) + k], k = 4 ulp32(max(d', m)) for the f32 evaluation of s.
+    A tile no box reaches reads +inf.  Menger depth 4 and a random depth-6 tree, 200x120, beam_back 0 and 2
+    (beam_back_held -1: the instrumented launch splats the same list), six cameras of tests/beam_cases.py.
+
+    m: the margin of DESIGN.md 3.1d, (2 sum |coef| + sum |bias|) 2^-20, with bias = coef o on an axis the ray
+    descends and coef (3 - o) on one it ascends (setup_ray's mirroring; test_beam_bound_random_camera_sweep's
+    unit drops the mirroring, which is off by |coef| (3 - 2 o) 2^-20, far above k).  It is evaluated twice: in
+    float64 from the float64 rays, which decides what a near-axis ray is and must agree with the f32 one to
+    1e-4 relative wherever every direction component is at least 1e-2, and in f32 with the kernel's own operations, which is the m of d' -- at the centre columns
+    u = 2 (x + 1/2) / W - 1 carries an absolute f32 error of 2^-24 into a direction component of 0.005, 1e-5
+    of that coef, which alone exceeds k wherever d is small (a camera at a box).
+    Near-axis rays (a float64 direction component below 1e-6) must read -inf or satisfy the bound; they are
+    at most 1 % of the pixels, checked from the float64 rays alone."""
+    from tests import beam_cases as bc
+    from tests import beam_model as bm
+    w, h = bc.W, bc.H
+    ran = 0
+    for pname, svo in _two_sided_pools().items():
+        lo, first = svo.masks_and_first()
+        depth = svo.depth()
+        for back in (0, 2):
+            rows = bm.splat_list_model(lo, first, depth, back)
+            assert rows is not None and len(rows) > 8
+            words = bm.box_words(rows)
+            ctr = bc.box_centre_world(rows[len(rows) // 2])
+            size_w = 32.0 * 2.0 ** -int(rows[len(rows) // 2][3])
+            cams = {
+                "inside the cube": bc.look((3.0, 9.0, -4.0), (-5.0, -8.0, 6.0)),
+                "1e-4 size outside a face": Camera(position=tuple(ctr + np.array([0.0, 0.5 * size_w * (1.0 + 2e-4), 0.0])),
+                                                   rotation=look_rotation((0.0, -1.0, 0.0), up=(0.0, 0.0, 1.0)), fov=60.0),
+                "far": bc.look(np.array([0.3, 0.5, -0.8]) / np.linalg.norm([0.3, 0.5, -0.8]) * 500.0, (0.0, 0.0, 0.0), 5.0),
+                "fov 160": Camera(position=(1.0, 9.0, 1.0), fov=160.0),
+                "fov 10": bc.look((0.0, 20.0, -40.0), (0.0, 0.0, 0.0), 10.0),
+                "along +z": bc.look((0.25, 4.0, -31.0), (0.25, 4.0, 10.0), 50.0),
+            }
+            m_ = RaytracingMaster(device=0, capacity_nodes=len(svo), config={"beam_back": back, "beam_back_held": -1})
+            starts = torch.empty(w * h, dtype=torch.float32, device="cuda")
+            try:
+                m_.SetSVOBuffer(svo)
+                for cname, cam in cams.items():
+                    what = f"{pname} back={back} {cname}"
+                    m_.UpdateShaderParameters(cam, w, h)
+                    m_.beam_starts_device(w, h, starts.data_ptr())
+                    m_.synchronize()
+                    s = starts.cpu().numpy().astype(np.float64)
+                    c2w, ip = cam.uniforms(w, h)
+                    bp = bc.cam_bp(cam, w, h)
+                    model = bm.splat_model(bp, words)
+                    # the float64 rays
+                    px = (np.arange(w * h) % w + 0.5) / w * 2 - 1
+                    py = (np.arange(w * h) // w + 0.5) / h * 2 - 1
+                    v = np.asarray(ip, np.float64) @ np.stack([px, py, np.zeros_like(px), np.ones_like(px)])
+                    d = (np.asarray(c2w, np.float64)[:3, :3] @ v[:3]).T
+                    d /= np.linalg.norm(d, axis=1, keepdims=True)
+                    o = bp["org"].astype(np.float64)
+                    near_axis = np.any(np.abs(d) < 1e-6, axis=1)
+                    assert near_axis.mean() <= 0.01, f"{what}: {near_axis.mean():.3f} near-axis rays"
+                    with np.errstate(divide="ignore"):
+                        coef = 1.0 / np.abs(d)
+                        m64 = (2 * coef.sum(1) + (coef * np.where(d > 0, 3.0 - o[None, :], o[None, :])).sum(1)) * 2.0 ** -20
+                    _, m32 = _ray_setup_f32(c2w, ip, w, h)
+                    m32 = m32.astype(np.float64)
+                    ok = np.all(np.abs(d) >= 1e-2, axis=1)     # u's f32 error is below 1e-5 of such a component
+                    assert ok.any() and np.all(np.abs(m32[ok] / m64[ok] - 1.0) < 1e-4), f"{what}: the two evaluations of m disagree"
+                    tile = (np.arange(w * h) // w >> 3) * bp["tiles_x"] + (np.arange(w * h) % w >> 3)
+                    hi, lo_ = model["hi_rule"][tile], model["lo_rule"][tile]
+                    with np.errstate(invalid="ignore"):
+                        dp = (s + m32) / (1.0 - 2.0 ** -16)
+                        big = np.maximum(np.abs(dp), m32)
+                        k = 4.0 * 2.0 ** (np.floor(np.log2(np.where(np.isfinite(big) & (big > 0), big, 1.0))) - 23)
+                        above = dp > hi * (1.0 + 2.0 ** -21) + k
+                        below = dp < np.where(np.isfinite(lo_), lo_ * (1.0 - 2.0 ** -21), lo_) - k
+                    free = near_axis & (s == -np.inf)
+                    bad = np.flatnonzero((above | below | np.isnan(dp)) & ~free)
+                    assert len(bad) == 0, (f"{what}: {len(bad)} pixels outside the envelope, first pixel {bad[0]}: s = {s[bad[0]]!r}, "
+                                           f"d' = {dp[bad[0]]!r}, [{lo_[bad[0]]!r}, {hi[bad[0]]!r}], k = {k[bad[0]]!r}")
+                    none = ~np.isfinite(model["hi_rule"][tile]) & (model["lo_rule"][tile] == np.inf)
+                    assert np.all(s[none & ~free] == np.inf), f"{what}: a start in a tile no box reaches"
+                    ran += 1
+            finally:
+                m_.close()
+    assert ran == 24

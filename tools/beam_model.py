@@ -38,7 +38,7 @@ def bind(L):
 
 
 def boxes_at(nodes, depth, leaves=False):
-    """Lower corners (SVO space) of the non-leaf nodes at `depth` (svo_rt.hip build_beam_boxes; this
+    """Lower corners (SVO space) of the non-leaf nodes at `depth` (svo_beam.h build_beam_boxes; this
     pool has its leaves at the deepest level only); leaves=True: every valid child at the last level
     (the voxels themselves when depth is the pool's, beam_back 0)."""
     lo = (nodes & np.uint64(0xFFFFFFFF)).astype(np.uint32)
