@@ -52,6 +52,58 @@ int svob_build_from_leaves(int depth, size_t n_leaves, const uint32_t *xyz, cons
 int svob_surface_leaves(int device, int sampler, int max_level, size_t *n_leaves,
                         uint64_t **morton_out, float **normals_out);
 
+/*
+ * Limits of the GPU leaf pass.  Zero means "default" in every field, and a NULL
+ * svob_limits is all defaults: svob_build_sampler and svob_surface_leaves are the
+ * _ex forms with NULL limits.  No field changes a result: every combination gives
+ * the same leaves, normals and pool; they move memory and time (and let a test reach
+ * the slab seams, the list regrowth and the stride loops on a small grid).
+ * Versioned by size like svo_config (svo_rt.h): a caller sets `size` =
+ * sizeof(svob_limits) as it was compiled, the library reads the fields that fit in it
+ * and takes the default of any later one; a size below the two header words or above
+ * this library's is SVOB -1 (argument error).
+ *
+ * Slab rule (svob_slab_rows): the leaf pass samples a byte grid of (n+2)^2 cells per
+ * z-plane, n = 2^(max_level-1), in slabs of `rows` leaf planes plus one halo plane
+ * below and one above:
+ *     rows = clamp(cell_bytes / (n+2)^2 - 2, 1, n)      (slab_rows == 0)
+ *     rows = clamp(slab_rows, 1, n)                     (slab_rows  > 0)
+ * A budget that holds fewer than three planes gives rows = 1: the buffer is then
+ * 3 (n+2)^2 bytes and EXCEEDS cell_bytes (max_level >= 15 at the default budget:
+ * 3 x 256 MiB at max_level 15, 3 x 4 TiB at max_level 22).
+ */
+typedef struct svob_limits {
+    uint32_t size;            /* sizeof(svob_limits) as compiled by the caller */
+    uint32_t reserved;        /* 0 */
+    uint64_t cell_bytes;      /* byte-grid budget of one slab, halo included (0: 512 MiB) */
+    uint64_t list_capacity;   /* initial capacity of the surface list, in leaves (0: max(1 Mi, 4 n^2));
+                                 a slab with more surface leaves regrows it to 1.25 x count + 1024 */
+    int32_t  slab_rows;       /* leaf planes per slab, overrides cell_bytes (0: the rule above); < 0: error */
+    int32_t  max_blocks;      /* cap on the blocks (of 256 threads) of each launch (0: 65,536); < 0: error */
+} svob_limits;
+
+/* What the leaf pass did; filled by the _ex entries when non-NULL.  `size` is set by the
+ * caller like svob_limits.size; at most `size` bytes are written. */
+typedef struct svob_report {
+    uint32_t size;              /* sizeof(svob_report) as compiled by the caller */
+    uint32_t slabs;             /* z-slabs sampled */
+    uint32_t slab_rows;         /* leaf planes per slab (the last slab may hold fewer) */
+    uint32_t relaunches;        /* classify launches repeated because a slab's count exceeded the capacity */
+    uint32_t normals_regrown;   /* 1: the list was re-allocated for the normal pass (all leaves > capacity) */
+    uint32_t reserved;          /* 0 */
+    uint64_t list_capacity;     /* capacity of the surface list when the last slab was classified */
+} svob_report;
+
+/* Leaf planes per slab for max_level under `limits` (NULL: defaults).  Pure host
+ * arithmetic, no GPU.  Returns rows >= 1, or a negative error code (svob_last_error). */
+int svob_slab_rows(int max_level, const svob_limits *limits);
+
+/* svob_build_sampler / svob_surface_leaves with limits (NULL: defaults) and an optional report. */
+int svob_build_sampler_ex(int device, int sampler, int max_level, const svob_limits *limits,
+                          svob_report *report, svob_result *out);
+int svob_surface_leaves_ex(int device, int sampler, int max_level, const svob_limits *limits,
+                           svob_report *report, size_t *n_leaves, uint64_t **morton_out, float **normals_out);
+
 /* Evaluate a sampler on the host (for tests): n points (x,y,z interleaved). */
 int svob_eval_sampler(int sampler, size_t n, const float *xyz, float *out);
 

@@ -16,6 +16,19 @@
 // and checked against the reference table's digest (tests/golden).
 // Arithmetic: C# float/double semantics, one IEEE rounding per operation
 // (-ffp-contract=off, no fast-math).
+// Limits of the GPU leaf pass (svob_limits, the _ex entry points; zero = default):
+//   cell_bytes     budget of one slab's byte grid, 512 MiB.  A slab holds `rows` leaf planes
+//                  plus a halo plane below and above: rows = clamp(cell_bytes / (n+2)^2 - 2,
+//                  1, n) (slab_rows_of, exported as svob_slab_rows).  One slab up to
+//                  max_level 10; 508 + 508 + 8 rows at max_level 11; one row from max_level
+//                  15, where three planes no longer fit and the buffer exceeds the budget.
+//   slab_rows      overrides the rule, clamped to [1, n].
+//   list_capacity  first capacity of the surface list, max(1 Mi, 4 n^2) leaves.  A slab
+//                  that counts more is classified again into a list of 1.25 x count + 1024
+//                  (classify_kernel stores only while k < cap); the normal pass
+//                  re-allocates when all leaves exceed the capacity.
+//   max_blocks     cap on each launch's blocks, 65,536; the kernels' stride loops cover the rest.
+// None of them changes a result.  svob_report says which of these paths a call took.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -605,7 +618,52 @@ int layout_from_sorted(int depth, std::vector<uint64_t> &codes, std::vector<V3> 
     return SVOB_OK;
 }
 
-int surface_leaves_gpu(int device, int type, int max_level, std::vector<uint64_t> &codes, std::vector<V3> &normals) {
+// ------------------------------------------------------------------ limits
+struct Limits {
+    uint64_t cell_bytes = 512ull << 20;
+    uint64_t list_capacity = 0;   // 0: max(1 Mi, 4 n^2)
+    int32_t slab_rows = 0;        // 0: from cell_bytes
+    int32_t max_blocks = 65536;
+};
+
+int read_limits(const svob_limits *in, Limits *out) {
+    *out = Limits();
+    if (!in) return SVOB_OK;
+    if (in->size < 2 * sizeof(uint32_t)) return fail(SVOB_ERR_ARG, "svob_limits.size must hold at least size and reserved");
+    if (in->size > sizeof(svob_limits))
+        return fail(SVOB_ERR_ARG, "svob_limits.size " + std::to_string(in->size) + " is larger than this library's (" +
+                                      std::to_string(sizeof(svob_limits)) + "): a newer ABI");
+    svob_limits k;
+    std::memset(&k, 0, sizeof k);   // fields past the caller's size: default
+    std::memcpy(&k, in, in->size);
+    if (k.slab_rows < 0) return fail(SVOB_ERR_ARG, "svob_limits.slab_rows must not be negative");
+    if (k.max_blocks < 0) return fail(SVOB_ERR_ARG, "svob_limits.max_blocks must not be negative");
+    if (k.list_capacity > SIZE_MAX / sizeof(uint64_t)) return fail(SVOB_ERR_ARG, "svob_limits.list_capacity is too large");
+    if (k.cell_bytes) out->cell_bytes = k.cell_bytes;
+    out->list_capacity = k.list_capacity;
+    out->slab_rows = k.slab_rows;
+    if (k.max_blocks) out->max_blocks = k.max_blocks;
+    return SVOB_OK;
+}
+
+// Leaf planes per z-slab: the byte grid holds rows + 2 planes of (n + 2)^2 cells (one halo
+// plane below, one above).  rows = clamp(cell_bytes / (n + 2)^2 - 2, 1, n); a budget of fewer
+// than three planes gives 1, and the buffer then exceeds the budget.  No subtraction below
+// three planes: the quotient is unsigned.
+int slab_rows_of(int n, const Limits &lim) {
+    if (lim.slab_rows > 0) return std::min(lim.slab_rows, n);
+    const uint64_t plane = ((uint64_t)n + 2) * ((uint64_t)n + 2);   // n <= 2^21: below 2^43
+    const uint64_t planes = lim.cell_bytes / plane;
+    if (planes < 3) return 1;
+    return (int)std::min<uint64_t>((uint64_t)n, planes - 2);
+}
+
+unsigned blocks_for(size_t items, const Limits &lim) {
+    return (unsigned)std::min<size_t>((items + 255) / 256, (size_t)lim.max_blocks);
+}
+
+int surface_leaves_gpu(int device, int type, int max_level, const Limits &lim, svob_report *rep,
+                       std::vector<uint64_t> &codes, std::vector<V3> &normals) {
     const int depth = max_level - 1;
     const int n = 1 << depth;
     const float size = std::ldexp(1.0f, -depth);
@@ -624,9 +682,9 @@ int surface_leaves_gpu(int device, int type, int max_level, std::vector<uint64_t
         if (dcount) (void)hipFree(dcount);
     };
     const size_t np2 = (size_t)n + 2;
-    // slab height: keep the byte grid under ~512 MiB
-    int slab = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, (512ull << 20) / (np2 * np2) - 2));
-    size_t cap = std::max<size_t>(1 << 20, (size_t)n * n * 4);
+    const int slab = slab_rows_of(n, lim);
+    size_t cap = lim.list_capacity ? (size_t)lim.list_capacity : std::max<size_t>(1 << 20, (size_t)n * n * 4);
+    uint32_t n_slabs = 0, n_relaunch = 0, regrown = 0;
     hipError_t e = hipMalloc(&ds, sizeof(Simplex3));
     if (e == hipSuccess) e = hipMemcpy(ds, &hs, sizeof(Simplex3), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMalloc(&cells, np2 * np2 * (size_t)(slab + 2));
@@ -638,7 +696,8 @@ int surface_leaves_gpu(int device, int type, int max_level, std::vector<uint64_t
         const int zc = std::min(slab, n - z0);
         const int zcells = zc + 2;
         const size_t ncell = np2 * np2 * (size_t)zcells;
-        const unsigned grid = (unsigned)std::min<size_t>((ncell + 255) / 256, 65536);
+        const unsigned grid = blocks_for(ncell, lim);
+        ++n_slabs;
         hipLaunchKernelGGL(sign_kernel, dim3(grid), dim3(256), 0, 0, ds, type, n, size, z0, zcells, cells);
         e = hipGetLastError();
         if (e != hipSuccess) { cleanup(); return fail(SVOB_ERR_HIP, std::string("builder sign launch: ") + hipGetErrorString(e)); }
@@ -646,7 +705,7 @@ int surface_leaves_gpu(int device, int type, int max_level, std::vector<uint64_t
             e = hipMemset(dcount, 0, sizeof(unsigned long long));
             if (e != hipSuccess) break;
             const size_t nl = (size_t)n * n * zc;
-            const unsigned g2 = (unsigned)std::min<size_t>((nl + 255) / 256, 65536);
+            const unsigned g2 = blocks_for(nl, lim);
             hipLaunchKernelGGL(classify_kernel, dim3(g2), dim3(256), 0, 0, cells, n, z0, zc, dcodes, dcount,
                                (unsigned long long)cap);
             e = hipGetLastError();
@@ -660,15 +719,18 @@ int surface_leaves_gpu(int device, int type, int max_level, std::vector<uint64_t
                 e = hipMemcpy(codes.data() + old, dcodes, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost);
                 break;
             }
+            // the kernel stored only the first cap codes (k < cap): grow the list and classify again
             (void)hipFree(dcodes);
             dcodes = nullptr;
             cap = (size_t)(cnt * 1.25) + 1024;
+            ++n_relaunch;
             e = hipMalloc(&dcodes, cap * sizeof(uint64_t));
             if (e != hipSuccess) break;
         }
         if (e != hipSuccess) { cleanup(); return fail(SVOB_ERR_HIP, std::string("builder classify: ") + hipGetErrorString(e)); }
     }
     std::sort(codes.begin(), codes.end());
+    const size_t cap_classified = cap;
     // normals of the sorted leaves
     normals.resize(codes.size());
     if (!codes.empty()) {
@@ -677,11 +739,12 @@ int surface_leaves_gpu(int device, int type, int max_level, std::vector<uint64_t
             (void)hipFree(dcodes);
             dcodes = nullptr;
             e = hipMalloc(&dcodes, codes.size() * sizeof(uint64_t));
+            regrown = 1;
         }
         if (e == hipSuccess) e = hipMemcpy(dcodes, codes.data(), codes.size() * sizeof(uint64_t), hipMemcpyHostToDevice);
         if (e == hipSuccess) e = hipMalloc(&dn, codes.size() * 3 * sizeof(float));
         if (e == hipSuccess) {
-            const unsigned g3 = (unsigned)std::min<size_t>((codes.size() + 255) / 256, 65536);
+            const unsigned g3 = blocks_for(codes.size(), lim);
             hipLaunchKernelGGL(normal_kernel, dim3(g3), dim3(256), 0, 0, ds, type, size, dcodes, codes.size(), dn);
             e = hipGetLastError();
         }
@@ -690,6 +753,18 @@ int surface_leaves_gpu(int device, int type, int max_level, std::vector<uint64_t
         if (e != hipSuccess) { cleanup(); return fail(SVOB_ERR_HIP, std::string("builder normals: ") + hipGetErrorString(e)); }
     }
     cleanup();
+    if (rep) {   // rep->size was checked by the entry point
+        svob_report k;
+        std::memset(&k, 0, sizeof k);
+        k.slabs = n_slabs;
+        k.slab_rows = (uint32_t)slab;
+        k.relaunches = n_relaunch;
+        k.normals_regrown = regrown;
+        k.list_capacity = cap_classified;
+        const size_t nb = std::min<size_t>(rep->size, sizeof k);
+        k.size = (uint32_t)nb;
+        std::memcpy(rep, &k, nb);
+    }
     return SVOB_OK;
 }
 
@@ -762,14 +837,31 @@ int svob_eval_sampler(int sampler, size_t n, const float *xyz, float *out) {
     return SVOB_OK;
 }
 
+int svob_slab_rows(int max_level, const svob_limits *limits) {
+    if (max_level < 2 || max_level > 22) return fail(SVOB_ERR_ARG, "max_level must be in [2, 22]");
+    Limits lim;
+    int rc = read_limits(limits, &lim);
+    if (rc) return rc;
+    return slab_rows_of(1 << (max_level - 1), lim);
+}
+
 int svob_surface_leaves(int device, int sampler, int max_level, size_t *n_leaves, uint64_t **morton_out,
                         float **normals_out) {
+    return svob_surface_leaves_ex(device, sampler, max_level, nullptr, nullptr, n_leaves, morton_out, normals_out);
+}
+
+int svob_surface_leaves_ex(int device, int sampler, int max_level, const svob_limits *limits, svob_report *report,
+                           size_t *n_leaves, uint64_t **morton_out, float **normals_out) {
     if (!n_leaves || !morton_out || !normals_out) return fail(SVOB_ERR_ARG, "null argument");
     int rc = check_sampler(sampler, max_level);
     if (rc) return rc;
+    Limits lim;
+    rc = read_limits(limits, &lim);
+    if (rc) return rc;
+    if (report && report->size < sizeof(uint32_t)) return fail(SVOB_ERR_ARG, "svob_report.size must hold at least size");
     std::vector<uint64_t> codes;
     std::vector<V3> normals;
-    rc = surface_leaves_gpu(device, sampler, max_level, codes, normals);
+    rc = surface_leaves_gpu(device, sampler, max_level, lim, report, codes, normals);
     if (rc) return rc;
     *n_leaves = codes.size();
     *morton_out = (uint64_t *)std::malloc(std::max<size_t>(1, codes.size()) * sizeof(uint64_t));
@@ -810,13 +902,22 @@ int svob_build_from_leaves(int depth, size_t n_leaves, const uint32_t *xyz, cons
 }
 
 int svob_build_sampler(int device, int sampler, int max_level, svob_result *out) {
+    return svob_build_sampler_ex(device, sampler, max_level, nullptr, nullptr, out);
+}
+
+int svob_build_sampler_ex(int device, int sampler, int max_level, const svob_limits *limits, svob_report *report,
+                          svob_result *out) {
     if (!out) return fail(SVOB_ERR_ARG, "null out");
     std::memset(out, 0, sizeof(*out));
     int rc = check_sampler(sampler, max_level);
     if (rc) return rc;
+    Limits lim;
+    rc = read_limits(limits, &lim);
+    if (rc) return rc;
+    if (report && report->size < sizeof(uint32_t)) return fail(SVOB_ERR_ARG, "svob_report.size must hold at least size");
     std::vector<uint64_t> codes;
     std::vector<V3> normals;
-    rc = surface_leaves_gpu(device, sampler, max_level, codes, normals);
+    rc = surface_leaves_gpu(device, sampler, max_level, lim, report, codes, normals);
     if (rc) return rc;
     const int depth = max_level - 1;
     if (codes.empty()) return empty_tree(depth, out);

@@ -19,6 +19,43 @@ class _Result(ctypes.Structure):
                 ("attachments", ctypes.POINTER(ctypes.c_uint32)), ("n_leaves", ctypes.c_size_t)]
 
 
+class _Limits(ctypes.Structure):
+    """svob_limits (include/svo_build.h): zero is the default of every field."""
+    _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("cell_bytes", ctypes.c_uint64),
+                ("list_capacity", ctypes.c_uint64), ("slab_rows", ctypes.c_int32), ("max_blocks", ctypes.c_int32)]
+
+
+class _Report(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("slabs", ctypes.c_uint32), ("slab_rows", ctypes.c_uint32),
+                ("relaunches", ctypes.c_uint32), ("normals_regrown", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("list_capacity", ctypes.c_uint64)]
+
+
+LIMIT_FIELDS = ("cell_bytes", "slab_rows", "list_capacity", "max_blocks")
+REPORT_FIELDS = ("slabs", "slab_rows", "relaunches", "normals_regrown", "list_capacity")
+
+
+def _limits(limits):
+    """None, or a mapping with any of LIMIT_FIELDS -> a svob_limits (None: NULL, all defaults)."""
+    if limits is None:
+        return None
+    unknown = set(limits) - set(LIMIT_FIELDS)
+    if unknown:
+        raise SvoError(f"unknown builder limits {sorted(unknown)}: the fields are {LIMIT_FIELDS}")
+    lim = _Limits(size=ctypes.sizeof(_Limits))
+    for k, v in limits.items():
+        setattr(lim, k, int(v))
+    return ctypes.byref(lim)
+
+
+def _new_report():
+    return _Report(size=ctypes.sizeof(_Report))
+
+
+def _report_dict(rep):
+    return {k: int(getattr(rep, k)) for k in REPORT_FIELDS}
+
+
 _blib = None
 
 
@@ -33,6 +70,10 @@ def blib():
         L.svob_build_sampler.argtypes = [i, i, i, ctypes.POINTER(_Result)]
         L.svob_build_from_leaves.argtypes = [i, sz, vp, vp, vp, ctypes.POINTER(_Result)]
         L.svob_surface_leaves.argtypes = [i, i, i, ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(vp)]
+        L.svob_build_sampler_ex.argtypes = [i, i, i, vp, vp, ctypes.POINTER(_Result)]
+        L.svob_surface_leaves_ex.argtypes = [i, i, i, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(vp),
+                                             ctypes.POINTER(vp)]
+        L.svob_slab_rows.argtypes = [i, vp]
         L.svob_eval_sampler.argtypes = [i, sz, vp, vp]
         L.svob_opensimplex_table.argtypes = [vp]
         L.svob_free.argtypes = [ctypes.POINTER(_Result)]
@@ -41,7 +82,7 @@ def blib():
         L.svob_free_ptr.restype = None
         L.svob_last_error.restype = ctypes.c_char_p
         for name in ("svob_build_sampler", "svob_build_from_leaves", "svob_surface_leaves", "svob_eval_sampler",
-                     "svob_opensimplex_table"):
+                     "svob_opensimplex_table", "svob_build_sampler_ex", "svob_surface_leaves_ex", "svob_slab_rows"):
             getattr(L, name).restype = i
         _blib = L
     return _blib
@@ -62,15 +103,26 @@ def _to_svodata(res, prefer_v1=True):
     return SVOData(nodes=nodes, attachments=att)
 
 
-def build_sampler_svo(sample_type, max_level, device=0, prefer_v1=True):
-    """NaiveCreator.Create(SampleFunctions.functions[sample_type], max_level)."""
+def slab_rows(max_level, limits=None):
+    """Leaf planes per z-slab of the GPU leaf pass (svob_slab_rows; host arithmetic, no GPU)."""
+    rows = blib().svob_slab_rows(int(max_level), _limits(limits))
+    if rows < 1:
+        _check(rows, "svob_slab_rows")
+    return rows
+
+
+def build_sampler_svo(sample_type, max_level, device=0, prefer_v1=True, limits=None, report=False):
+    """NaiveCreator.Create(SampleFunctions.functions[sample_type], max_level).
+    limits: None or a mapping with any of LIMIT_FIELDS (svob_limits; they never change the
+    result).  report=True: returns (svo, dict of REPORT_FIELDS)."""
     res = _Result()
-    _check(blib().svob_build_sampler(int(device), int(sample_type), int(max_level), ctypes.byref(res)),
-           "svob_build_sampler")
+    rep = _new_report()
+    _check(blib().svob_build_sampler_ex(int(device), int(sample_type), int(max_level), _limits(limits),
+                                        ctypes.byref(rep), ctypes.byref(res)), "svob_build_sampler")
     try:
         data = _to_svodata(res, prefer_v1)
         data.n_leaves = int(res.n_leaves)
-        return data
+        return (data, _report_dict(rep)) if report else data
     finally:
         blib().svob_free(ctypes.byref(res))
 
@@ -90,19 +142,22 @@ def build_from_leaves(depth, xyz, normals, colors=None, prefer_v1=True):
         blib().svob_free(ctypes.byref(res))
 
 
-def surface_leaves(sample_type, max_level, device=0):
-    """(Morton codes uint64[n], normals float32[n, 3]) of the surface voxels."""
+def surface_leaves(sample_type, max_level, device=0, limits=None, report=False):
+    """(Morton codes uint64[n], normals float32[n, 3]) of the surface voxels; with report=True a
+    third item, the dict of REPORT_FIELDS.  limits: as build_sampler_svo."""
     n = ctypes.c_size_t()
     mp = ctypes.c_void_p()
     npp = ctypes.c_void_p()
-    _check(blib().svob_surface_leaves(int(device), int(sample_type), int(max_level), ctypes.byref(n),
-                                      ctypes.byref(mp), ctypes.byref(npp)), "svob_surface_leaves")
+    rep = _new_report()
+    _check(blib().svob_surface_leaves_ex(int(device), int(sample_type), int(max_level), _limits(limits),
+                                         ctypes.byref(rep), ctypes.byref(n), ctypes.byref(mp), ctypes.byref(npp)),
+           "svob_surface_leaves")
     try:
         codes = np.ctypeslib.as_array(ctypes.cast(mp, ctypes.POINTER(ctypes.c_uint64)), shape=(n.value,)).copy() \
             if n.value else np.zeros(0, np.uint64)
         nrm = np.ctypeslib.as_array(ctypes.cast(npp, ctypes.POINTER(ctypes.c_float)), shape=(n.value, 3)).copy() \
             if n.value else np.zeros((0, 3), np.float32)
-        return codes, nrm
+        return (codes, nrm, _report_dict(rep)) if report else (codes, nrm)
     finally:
         blib().svob_free_ptr(mp)
         blib().svob_free_ptr(npp)

@@ -121,10 +121,15 @@ def test_gpu_classification_matches_host(sampler, max_level):
     host = _host_surface(sampler, max_level)
     from raytracingtest_amd.builder import morton
     assert np.array_equal(np.sort(morton(host)), codes)
-    # normals: -Normalize(finite differences), recomputed on the host
+    np.testing.assert_array_equal(nrm, _host_normals(sampler, max_level, host))
+
+
+def _host_normals(sampler, max_level, host):
+    """-Normalize(finite differences) (NaiveCreator.cs:58-63) of the leaves `host` (integer xyz),
+    recomputed with the host sampler, in Morton order."""
+    from raytracingtest_amd.builder import morton, normalize_unity
     d = max_level - 1
     size = np.float32(2.0 ** -d)
-    from raytracingtest_amd.builder import normalize_unity
     xyz = host[np.argsort(morton(host))].astype(np.float32)
     p = (np.float32(1) + xyz * size + size / np.float32(2)).astype(np.float32)
     h = np.float32(0.001)
@@ -134,12 +139,39 @@ def test_gpu_classification_matches_host(sampler, max_level):
         q = p.copy()
         q[:, ax] = (q[:, ax] - h).astype(np.float32)
         diffs.append((nb.eval_sampler(sampler, q) - s0).astype(np.float32))
-    ref = -normalize_unity(np.stack(diffs, 1))
-    np.testing.assert_array_equal(nrm, ref)
+    return -normalize_unity(np.stack(diffs, 1))
+
+
+@pytest.fixture(scope="module")
+def depth10_surface():
+    """The benchmark grid's leaf pass (Custom1, max_level 11, 1024^3) twice: with the default limits
+    (slabs of 508 + 508 + 8 leaf planes, seams at z = 508 and z = 1016) and with a 2 GiB byte-grid
+    budget (one slab of 1026^3 cells, 1.08 GB).  (codes, normals, report) of each."""
+    torch = pytest.importorskip("torch")
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    return {"default": nb.surface_leaves(nb.CUSTOM1, 11, report=True),
+            "one_slab": nb.surface_leaves(nb.CUSTOM1, 11, limits={"cell_bytes": 2 << 30}, report=True)}
 
 
 @pytest.mark.gpu
-def test_gpu_build_depth10_custom1():
+def test_gpu_depth10_three_slabs_equal_one_slab(depth10_surface):
+    """The benchmark pool's own seams: three slabs and one slab give the same leaves and normals,
+    bit for bit.  No host model of 1026^3 samples: tests/test_builder_limits.py ties one slab to
+    the host model at 64^3, this ties three slabs to one at the planes the benchmark crosses."""
+    codes3, nrm3, rep3 = depth10_surface["default"]
+    codes1, nrm1, rep1 = depth10_surface["one_slab"]
+    assert nb.slab_rows(11) == 508 and nb.slab_rows(11, {"cell_bytes": 2 << 30}) == 1024
+    assert (rep3["slabs"], rep3["slab_rows"]) == (3, 508)
+    assert (rep1["slabs"], rep1["slab_rows"]) == (1, 1024)
+    assert rep3["relaunches"] == 0 and rep1["relaunches"] == 0   # 4 n^2 leaves hold either
+    assert len(codes3) > 1_000_000
+    assert np.array_equal(codes3, codes1)
+    assert nrm3.tobytes() == nrm1.tobytes()
+
+
+@pytest.mark.gpu
+def test_gpu_build_depth10_custom1(depth10_surface):
     torch = pytest.importorskip("torch")
     if not torch.cuda.is_available():
         pytest.skip("no GPU")
@@ -148,6 +180,9 @@ def test_gpu_build_depth10_custom1():
     assert svo.n_leaves > 1_000_000
     lo, first = svo.masks_and_first()
     assert lo[0] & 0xFF00   # root has children
+    codes = depth10_surface["default"][0]
+    assert svo.n_leaves == len(codes)
+    assert np.all(codes[1:] > codes[:-1])   # strictly increasing: sorted, no leaf twice
 
 
 def test_python_sampler_matches_native_host_sampler():
