@@ -624,6 +624,62 @@ int svo_get_skybox(svo_ctx *ctx, int *width, int *height, uint32_t *flags);     
 int svo_sample_sky(svo_ctx *ctx, const float *d_dirs, size_t n, float *d_rgba, void *stream);
 int svo_sample_sky_host(svo_ctx *ctx, const float *dirs, size_t n, float *rgba);
 
+/* Ambient: sky light with ambient occlusion (opt-in; off by default, and with it off every byte is what
+ * it was).  The reference has no ambient term (a documented deviation): it lights a hit with one
+ * directional light, so a pixel that faces away from it, or that the shadow pass occludes, is black.
+ *
+ * The ambient rule (csrc/svo_ambient.h; numpy: ambient.py).  Every operation is one IEEE f32 rounding,
+ * no fma.  Direction tables for N in {4, 8, 16}: entry k is (a, b, c) with r = sqrt((k + 0.5) / N),
+ * phi = (k + 0.5) pi (3 - sqrt 5), a = r cos phi, b = r sin phi, c = sqrt(1 - r r), computed in float64 and
+ * rounded once; the 28 triples committed in csrc/svo_ambient.h are the truth.  Every |component| >= 2^-10
+ * and c > 0.  Variant v in 0..7: if v & 4 swap a and b, then v & 3 times (a, b) -> (-b, a); all exact.
+ * Per traced ray (o, d) and its hit (t, hit_scale, voxel key):
+ *  1. steps 1-3 of the bounce rule above give the entry axis g, out = d_g > 0 ? -1 : +1 and the origin
+ *     (P off the axis g, face_g + out side 2^-6 on it).
+ *  2. direction k: dir_g = out c, dir_{(g+1)%3} = a, dir_{(g+2)%3} = b of the variant's entry k.
+ *  3. the ambient ray is {origin, t_max = radius, dir, 0}, traced as svo_trace_rays traces it with flags 0
+ *     (classify, the clamp -- the identity here --, the walk, then the t (1 / 64) <= t_max filter on the
+ *     finished record; no early exit on radius).  radius: +inf, or positive and finite, in world units.
+ *  4. the ray is open iff its record has neither flag bit 0 nor bit 4.  A record with only the
+ *     iteration-cap or stack-overflow flag is open; a hit at t = 0 (an origin inside a neighbouring
+ *     voxel) counts as occluded.
+ * Fold per hit pixel: alb = the primary record's DXT albedo; direct = the pixel's colour as rendered with
+ * ambient off (black if the record carries flag bit 3); S = (0, 0, 0); for k = 0 .. N - 1 in that order,
+ * if ray k is open, S += sky of its direction (the gradient of dir_y, or the skybox rule on dir with a
+ * texture set); A = S (1 / N); res_c = direct_c + (ambient_c alb_c) A_c; alpha 1.
+ * Only rgba, rgba8 and rgb8 change (and through them a progressive accumulation); hits, compact, position,
+ * voxel and hitmask stay the primary ray's, a shadow pass's bit 3 included; miss pixels are untouched.
+ *
+ * svo_set_ambient: ambient three finite numbers in [0, 4], n_rays in {0, 4, 8, 16}, radius +inf or finite
+ * and > 0, variant < 8; anything else, NaN included: SVO_ERR_ARG, checked before the context is read or a
+ * device touched.  NULL ambient, all-zero ambient or n_rays 0: off.  Not a svo_config field: svo_config
+ * never changes results.  Leaves the dispatch-order state, tile costs, beam starts, view-change detection
+ * and kernel-timing records alone (SVO_STAGE_KERNEL still brackets the primary kernel only).  The variant
+ * is the same for every pixel of a launch; svo_render_progressive(_async) use (variant + sample) & 7, so
+ * an accumulated frame sees up to 8 N directions.  The pass runs behind the primary launch and its shadow
+ * pass (all three shadow_form's), before the sky pass.  Served: svo_render, svo_render_device,
+ * svo_render_frame (any band, layout and stream) and svo_render_progressive(_async); it combines with
+ * SVO_OPT_SHADOW_RAYS and a skybox texture.  svo_count_fetches, svo_beam_starts and svo_assemble_frame are
+ * unaffected; a launch that writes no colour output has no ambient pass.  Stated limits, each SVO_ERR_STATE
+ * before anything is enqueued: a render with reflection on, a render with LOD on, svo_render_samples; and
+ * a non-off setting on a multi-device context.  svo_get_ambient: every pointer may be NULL.
+ *
+ * svo_ambient_rays: out[i n_rays + k] = ray k of rays[i] if hits[i] has flag bit 0, else the dead ray
+ * (svo_bounce_rays') for every k.  flags: SVO_QUERY_RAW_DIRECTIONS only (how rays[i] was traced).  n_rays
+ * in {4, 8, 16}; n n_rays <= 2^31 - 1.  Writes nothing past n n_rays entries; the output must not overlap
+ * an input (SVO_ERR_ARG).  NULL pointers, unknown flag bits, a bad n_rays, radius or variant: SVO_ERR_ARG
+ * before any device is touched; n == 0: SVO_OK, nothing launched.  Reads no pool.  Ray lists 16-byte
+ * aligned, records and keys 8-byte.  A multi-device context runs it on devices[0].  Asynchronous on
+ * `stream`; the host form blocks. */
+enum { SVO_AMBIENT_MAX_RAYS = 16 };
+int svo_set_ambient(svo_ctx *ctx, const float ambient[3], int n_rays, float radius, uint32_t variant);   /* NULL / 0 = off (default) */
+int svo_get_ambient(svo_ctx *ctx, float ambient[3], int *n_rays, float *radius, uint32_t *variant);
+int svo_ambient_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
+                     const uint64_t *d_voxel, int n_rays, float radius, uint32_t variant, svo_ray *d_rays_out,
+                     void *stream);
+int svo_ambient_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
+                          const uint64_t *voxel, int n_rays, float radius, uint32_t variant, svo_ray *rays_out);
+
 /* Information about the uploaded pool. */
 int svo_get_info(svo_ctx *ctx, size_t *n_nodes, int *max_depth, int *device);
 

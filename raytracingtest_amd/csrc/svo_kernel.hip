@@ -13,6 +13,7 @@
 // placement) were removed (DESIGN.md 5.1 keeps their numbers).
 #include "svo_traverse.h"
 #include "svo_reflect.h"
+#include "svo_ambient.h"
 
 #include <hipcub/hipcub.hpp>   // ordered ray queries: the toolchain's device radix sort (launch_query_sort)
 
@@ -1866,6 +1867,147 @@ __global__ __launch_bounds__(TILE) void reflect_list_sky_kernel(LaunchParams p, 
     reflect_list_body<MODE, GUARD, FA, true>(p, list, count, sr, sg, sb, max_bounces, tex);
 }
 
+// ---------------------------------------------------------- ambient pass
+// svo_ambient_rays: entry j = i * n_rays + k of the output is ray k of rays[i] (svo_ambient.h
+// ambient_entry).  One thread per entry, two 16-byte stores; the output is n_rays times the input and
+// must not overlap it (checked by the host).  Reads no pool.
+__global__ __launch_bounds__(256) void ambient_rays_kernel(const QueryRay *__restrict__ rays, uint32_t n, uint32_t flags,
+                                                           const Hit *__restrict__ hits,
+                                                           const unsigned long long *__restrict__ voxel, int n_rays,
+                                                           float radius, uint32_t variant, QueryRay *__restrict__ out) {
+    const size_t j = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (j >= (size_t)n * (size_t)n_rays) return;
+    const uint32_t i = (uint32_t)(j / (uint32_t)n_rays);
+    const int k = (int)(j - (size_t)i * (uint32_t)n_rays);
+    const uint4 *src = reinterpret_cast<const uint4 *>(rays) + 2 * (size_t)i;
+    const uint4 a = src[0], b = src[1];
+    const uint2 *rec = reinterpret_cast<const uint2 *>(hits + i);
+    const uint2 h0 = rec[0], h1 = rec[1], h2 = rec[2];
+    const uint32_t ray[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
+    const uint32_t hit[6] = { h0.x, h0.y, h1.x, h1.y, h2.x, h2.y };
+    uint32_t o[8];
+    svo_ambient::ambient_entry(ray, hit, voxel[i], (flags & QUERY_RAW) != 0, n_rays, k, radius, variant, o);
+    uint4 *dst = reinterpret_cast<uint4 *>(out) + 2 * j;
+    dst[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// svo_set_ambient: sky light with ambient occlusion, as one more pass over the primary
+// launch's compacted hit list -- reflect_list_kernel's shape, one wave per 64 list entries, the same
+// [slot][lane] LDS stack.  A lane starts from its pixel's camera ray and primary record (out.hits,
+// out.voxel): direct = the ambient-off colour recomputed from the record (black with flag bit 3, the
+// shadow pass's mark), and the entry face of the voxel (svo_reflect.h entry_face) gives the common origin
+// of its n_rays rays.  The k loop is outermost and wave-uniform: all lanes trace table entry k together
+// (svo_ambient.h ambient_dir, the entry read through a scalar load), as a query traces {origin, radius,
+// dir, 0} with flags 0: classify (only the origin can fail it), the clamp (the identity on a table
+// direction), the primary rays' loop, then the t (1 / 64) <= radius filter on the finished record -- no
+// early exit.  A ray with no hit left is open and adds the sky of its direction to S, in k order, in
+// registers, with no cross-lane sum.  res = direct + (ambient * albedo) * (S / n_rays).  trace_lean runs
+// under `if (go)` only when the wave's ballot of `go` is non-zero, as in the reflection pass.  Hit pixels'
+// colours are overwritten with plain stores; records, keys, positions and masks stay the primary ray's.
+template <int MODE, bool GUARD, bool FA, bool SKY>
+__device__ __forceinline__ void ambient_list_body(const LaunchParams p, const uint32_t *__restrict__ list,
+                                                  const uint32_t *__restrict__ count, float ar, float ag, float ab,
+                                                  int n_rays, float radius, uint32_t variant,
+                                                  const svo_sky::Texture &tex) {
+    extern __shared__ uint2 stk_base[];
+    const int lane = (int)threadIdx.x;
+    const uint32_t k = blockIdx.x * TILE + (uint32_t)lane;
+    const uint32_t n = *count;
+    if (blockIdx.x * TILE >= n) return;   // the whole wave
+    const bool mine = k < n;
+    const uint32_t px = mine ? list[k] : 0u;
+    const int x = (int)(px % (uint32_t)p.width), lr = (int)(px / (uint32_t)p.width);
+    const int gy = global_row(p, lr);
+    const size_t i = out_index(p, lr, gy, x);
+    float org[3] = {0.0f, 0.0f, 0.0f}, res[3] = {0.0f, 0.0f, 0.0f}, w[3] = {0.0f, 0.0f, 0.0f};
+    float out = 1.0f;
+    int g = 0;
+    bool go = false;
+    if (mine) {
+        const uint2 *rec = reinterpret_cast<const uint2 *>(p.out.hits + i);
+        const uint2 h0 = rec[0], h1 = rec[1], h2 = rec[2];
+        const float nrm[3] = {__uint_as_float(h1.y), __uint_as_float(h2.x), __uint_as_float(h2.y)};
+        float o[3], d[3];
+        camera_ray(p.cam, p.width, p.height, x, gy, o, d);
+        const uint2 a = p.att[h0.x];
+        float alb[3];
+        decode_dxt(a.x, a.y, (int)(h0.y & 0xFFu), alb);
+        if (!((h0.y >> 16) & 8u)) shade_hit(p.cam, nrm, alb, res);
+        w[0] = ar * alb[0]; w[1] = ag * alb[1]; w[2] = ab * alb[2];
+        g = svo_reflect::entry_face(o, d, __uint_as_float(h1.x), (int)((h0.y >> 8) & 0xFFu), p.out.voxel[i], org, &out);
+        go = finite_f32(org[0]) && finite_f32(org[1]) && finite_f32(org[2]);   // the query's classify
+    }
+    float S[3] = {0.0f, 0.0f, 0.0f};
+    uint2 *stk = stk_base + lane;
+    if (LM_OF(go) != 0) {   // wave-uniform
+#pragma nounroll
+        for (int kk = 0; kk < n_rays; ++kk) {
+            if (go) {
+                float dir[3];
+                svo_ambient::ambient_dir(n_rays, kk, variant, g, out, dir);
+                Ray r;
+                setup_ray(org, dir, r);
+                FRay f;
+                to_fray(r, f);
+                trace_lean<MODE, GUARD, false, FA>(p, f, stk);
+                from_fray(f, r);
+                bool hit = r.scale < S_MAX;
+                if (hit) {
+                    const float t_min = r.t_min * 32.0f;
+                    hit = (t_min * 64.0f) * (1.0f / 64.0f) <= radius;
+                }
+                if (!hit) {   // open
+                    float col[3];
+                    if (SKY) svo_sky::sample(tex, dir, col);
+                    else sky(r.dir_y, col);
+                    S[0] = S[0] + col[0];
+                    S[1] = S[1] + col[1];
+                    S[2] = S[2] + col[2];
+                }
+            }
+        }
+    }
+    if (!mine) return;
+    const float inv_n = 1.0f / (float)n_rays;   // exact: a power of two
+    res[0] = res[0] + w[0] * (S[0] * inv_n);
+    res[1] = res[1] + w[1] * (S[1] * inv_n);
+    res[2] = res[2] + w[2] * (S[2] * inv_n);
+    if (p.out.rgba) p.out.rgba[i] = make_float4(res[0], res[1], res[2], 1.0f);
+    if (p.out.rgba8 || p.out.rgb8) {
+        const uint32_t c = pack_rgba8(res[0], res[1], res[2]);
+        if (p.out.rgba8) p.out.rgba8[i] = c;
+        if (p.out.rgb8) {
+            uint8_t *dst = p.out.rgb8 + 3 * i;
+            dst[0] = (uint8_t)c;
+            dst[1] = (uint8_t)(c >> 8);
+            dst[2] = (uint8_t)(c >> 16);
+        }
+    }
+}
+
+struct AmbientKernelArgs {   // one kernel argument beside LaunchParams (which does not grow)
+    float ambient[3];
+    int n_rays;
+    float radius;
+    uint32_t variant;
+};
+
+template <int MODE, bool GUARD, bool FA>
+__global__ __launch_bounds__(TILE) void ambient_list_kernel(LaunchParams p, const uint32_t *__restrict__ list,
+                                                            const uint32_t *__restrict__ count, AmbientKernelArgs a) {
+    ambient_list_body<MODE, GUARD, FA, false>(p, list, count, a.ambient[0], a.ambient[1], a.ambient[2], a.n_rays, a.radius,
+                                              a.variant, svo_sky::Texture{});
+}
+
+template <int MODE, bool GUARD, bool FA>
+__global__ __launch_bounds__(TILE) void ambient_list_sky_kernel(LaunchParams p, const uint32_t *__restrict__ list,
+                                                                const uint32_t *__restrict__ count, AmbientKernelArgs a,
+                                                                svo_sky::Texture tex) {
+    ambient_list_body<MODE, GUARD, FA, true>(p, list, count, a.ambient[0], a.ambient[1], a.ambient[2], a.n_rays, a.radius,
+                                             a.variant, tex);
+}
+
 // ------------------------------------------------------------------ skybox
 // svo_set_skybox: the sky pass behind the primary launch.  One wave64 per 8x8 tile of the
 // launch's rows, in plain tile order (the pass has no heavy tiles to put first).  The tile's hit mask is
@@ -3023,6 +3165,63 @@ hipError_t launch_reflect(const LaunchParams &p, const ReflectArgs &ra, int stac
     LaunchParams q = p;
     q.out.hitmask = nullptr;
     return stack_mode == 0 ? launch_reflect_mode<0>(q, list, cnt, ra, stream) : launch_reflect_mode<1>(q, list, cnt, ra, stream);
+}
+
+template <int MODE>
+static hipError_t launch_ambient_mode(const LaunchParams &q, const uint32_t *list, const uint32_t *cnt, const AmbientArgs &aa,
+                                      hipStream_t stream) {
+    const size_t lds = (size_t)q.slots * TILE * sizeof(uint2);
+    const dim3 grid((unsigned)(((size_t)q.width * (size_t)q.local_rows + TILE - 1) / TILE)), block(TILE);
+    AmbientKernelArgs a;
+    for (int k = 0; k < 3; ++k) a.ambient[k] = aa.ambient[k];
+    a.n_rays = aa.n_rays;
+    a.radius = aa.radius;
+    a.variant = aa.variant;
+    // guarded pools and fetch_all select the loop as the reflection pass does
+    if (aa.sky.texels) {
+        if (q.guard)
+            hipLaunchKernelGGL((ambient_list_sky_kernel<MODE, true, false>), grid, block, lds, stream, q, list, cnt, a, aa.sky);
+        else if (q.fetch_all)
+            hipLaunchKernelGGL((ambient_list_sky_kernel<MODE, false, true>), grid, block, lds, stream, q, list, cnt, a, aa.sky);
+        else
+            hipLaunchKernelGGL((ambient_list_sky_kernel<MODE, false, false>), grid, block, lds, stream, q, list, cnt, a, aa.sky);
+    }
+    else if (q.guard)
+        hipLaunchKernelGGL((ambient_list_kernel<MODE, true, false>), grid, block, lds, stream, q, list, cnt, a);
+    else if (q.fetch_all)
+        hipLaunchKernelGGL((ambient_list_kernel<MODE, false, true>), grid, block, lds, stream, q, list, cnt, a);
+    else
+        hipLaunchKernelGGL((ambient_list_kernel<MODE, false, false>), grid, block, lds, stream, q, list, cnt, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ambient(const LaunchParams &p, const AmbientArgs &aa, int stack_mode, hipStream_t stream) {
+    if (!p.out.hits || !p.out.voxel || !aa.scratch || !svo_ambient::valid_count(aa.n_rays) || aa.variant > 7u ||
+        p.width <= 0 || p.local_rows <= 0)
+        return hipErrorInvalidValue;
+    // the hit list in the scratch whose head holds the launch's hit masks (rebuilt behind a compacted
+    // shadow pass too: the same masks give the same list)
+    hipError_t e = launch_pack<true>(nullptr, p.width, p.local_rows, aa.scratch, stream);
+    if (e != hipSuccess) return e;
+    const int n = ((p.width + 7) / 8) * ((p.local_rows + 7) / 8);
+    const SparseLayout L = sparse_layout(n, p.width * p.local_rows, 4);
+    const uint8_t *base = reinterpret_cast<const uint8_t *>(aa.scratch);
+    const uint32_t *list = reinterpret_cast<const uint32_t *>(base + L.rgb);
+    const uint32_t *cnt = reinterpret_cast<const uint32_t *>(base + L.offsets) + n;
+    LaunchParams q = p;
+    q.out.hitmask = nullptr;
+    return stack_mode == 0 ? launch_ambient_mode<0>(q, list, cnt, aa, stream) : launch_ambient_mode<1>(q, list, cnt, aa, stream);
+}
+
+hipError_t launch_ambient_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
+                               const unsigned long long *voxel, int n_rays, float radius, uint32_t variant, QueryRay *out,
+                               hipStream_t stream) {
+    if (!rays || !hits || !voxel || !out || !svo_ambient::valid_count(n_rays) || variant > 7u) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const size_t total = (size_t)n * (size_t)n_rays;
+    hipLaunchKernelGGL(ambient_rays_kernel, dim3((unsigned)((total + 255u) / 256u)), dim3(256), 0, stream, rays, n, flags, hits,
+                       voxel, n_rays, radius, variant, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_sky_fill(const LaunchParams &p, const svo_sky::Texture &sky, const unsigned long long *masks,

@@ -31,16 +31,11 @@ SVO_REFLECT_FN void clamp_direction(float d[3], bool raw) {
         if (std::fabs(d[k]) < eps) d[k] = std::copysign(eps, d[k]);
 }
 
-// The bounce ray of the ray (o, d) AS TRACED (a query's direction after the clamp) and its hit:
-// t the record's t (2048 x SVO t), n the record's normal, scale its hit_scale, key its voxel key.
-//  1. box:       side = 2^(scale - 18), lo = c side - 16, hi = lo + side (c: the key's coordinates)
-//  2. entry face: face_k = d_k > 0 ? lo_k : hi_k, te_k = (face_k - o_k) (1 / d_k), g = the axis of the
-//                 largest te (ordered compares from g = 0: a NaN never wins), out = d_g > 0 ? -1 : +1
-//  3. origin:    P = o + (t / 64) d off the axis g, face_g + out side 2^-6 on it
-//  4. direction: r = d - 2 (n . d) n, and r_g negated if it points into the face; not renormalised
-// org and dir may alias o and d.
-SVO_REFLECT_FN void bounce(const float o[3], const float d[3], float t, const float n[3], int scale,
-                           unsigned long long key, float org[3], float dir[3]) {
+// Steps 1-3 of the bounce rule below, shared with the ambient rule (svo_ambient.h): the entry axis g
+// (returned), *out = d_g > 0 ? -1 : +1, and org = the origin of a ray that leaves through that face.
+// org may alias o; d is only read.
+SVO_REFLECT_FN int entry_face(const float o[3], const float d[3], float t, int scale, unsigned long long key,
+                              float org[3], float *out) {
     const float side = std::ldexp(1.0f, scale - 18);
     float face[3], te[3];
     for (int k = 0; k < 3; ++k) {
@@ -56,18 +51,36 @@ SVO_REFLECT_FN void bounce(const float o[3], const float d[3], float t, const fl
     if (te[2] > te_g) { g = 2; te_g = te[2]; }
     const float d_g = g == 0 ? d[0] : g == 1 ? d[1] : d[2];
     const float face_g = g == 0 ? face[0] : g == 1 ? face[1] : face[2];
-    const float out = d_g > 0.0f ? -1.0f : 1.0f;
+    const float sgn = d_g > 0.0f ? -1.0f : 1.0f;
     const float tw = t * (1.0f / 64.0f);
+    const float org_g = face_g + sgn * (side * 0x1p-6f);
+    for (int k = 0; k < 3; ++k) {
+        const float p = o[k] + tw * d[k];
+        org[k] = k == g ? org_g : p;
+    }
+    *out = sgn;
+    return g;
+}
+
+// The bounce ray of the ray (o, d) AS TRACED (a query's direction after the clamp) and its hit:
+// t the record's t (2048 x SVO t), n the record's normal, scale its hit_scale, key its voxel key.
+//  1. box:       side = 2^(scale - 18), lo = c side - 16, hi = lo + side (c: the key's coordinates)
+//  2. entry face: face_k = d_k > 0 ? lo_k : hi_k, te_k = (face_k - o_k) (1 / d_k), g = the axis of the
+//                 largest te (ordered compares from g = 0: a NaN never wins), out = d_g > 0 ? -1 : +1
+//  3. origin:    P = o + (t / 64) d off the axis g, face_g + out side 2^-6 on it
+//  4. direction: r = d - 2 (n . d) n, and r_g negated if it points into the face; not renormalised
+// org and dir may alias o and d.
+SVO_REFLECT_FN void bounce(const float o[3], const float d[3], float t, const float n[3], int scale,
+                           unsigned long long key, float org[3], float dir[3]) {
+    float out;
+    const int g = entry_face(o, d, t, scale, key, org, &out);   // writes org only: d and n are still the inputs
     float dn = n[0] * d[0];
     dn = dn + n[1] * d[1];
     dn = dn + n[2] * d[2];
     const float dn2 = 2.0f * dn;
-    const float org_g = face_g + out * (side * 0x1p-6f);
     for (int k = 0; k < 3; ++k) {
-        const float p = o[k] + tw * d[k];
         float r = d[k] - dn2 * n[k];
         if (k == g && ((out > 0.0f && r < 0.0f) || (out < 0.0f && r > 0.0f))) r = -r;
-        org[k] = k == g ? org_g : p;
         dir[k] = r;
     }
 }

@@ -41,6 +41,7 @@
 #include <vector>
 
 #include "svo_rt.h"
+#include "svo_ambient.h"
 #include "svo_beam.h"
 #include "svo_lod.h"
 #include "svo_sched.h"
@@ -274,6 +275,13 @@ struct svo_ctx {
     // device, one float4 per texel; the sky pass reads the tile hit masks from the caller's array or from
     // the head of d_shadow_list (the shadow forms' and the reflection pass's scratch)
     svo_sky::Texture sky{nullptr, 0, 0, 0u};
+    // ambient term of the renders (svo_set_ambient; n_rays 0 or ambient 0: off -- DESIGN.md 3.2e): the pass
+    // shares the reflection pass's scratch (the two never run together).  ambient_step: the sample index a
+    // progressive render adds to the variant for its one launch, 0 elsewhere
+    float ambient[3] = {0.0f, 0.0f, 0.0f};
+    int ambient_rays = 0;
+    float ambient_radius = std::numeric_limits<float>::infinity();
+    uint32_t ambient_variant = 0, ambient_step = 0;
     // diagnostics (the library's only environment switches, read once at svo_create):
     // SVO_DEBUG bit 0 the loop-form / class-table decision trace, bit 1 the order each launch
     // takes; SVO_WAVE_LOG=<file> the per-wave record; SVO_BEAM_DIAG the splat's timing variants
@@ -1055,6 +1063,37 @@ int reflect_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsign
     return SVO_OK;
 }
 
+bool ambient_on(const svo_ctx *ctx) {
+    return ctx->ambient_rays > 0 && (ctx->ambient[0] != 0.0f || ctx->ambient[1] != 0.0f || ctx->ambient[2] != 0.0f);
+}
+
+// The ambient pass's inputs: the reflection pass's (reflect_scratch).  Behind the
+// compacted shadow form the masks already lie at the head of the shared scratch: they are no caller's.
+int ambient_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p, unsigned long long **caller_mask) {
+    const int rc = reflect_scratch(ctx, L, p, caller_mask);
+    if (rc) return rc;
+    if (*caller_mask == reinterpret_cast<unsigned long long *>(ctx->d_shadow_list)) *caller_mask = nullptr;
+    return SVO_OK;
+}
+
+// Behind the primary launch and its shadow pass: compact the hit pixels and add each one's ambient term.
+int ambient_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsigned long long *caller_mask) {
+    if (caller_mask)
+        HIP_TRY(hipMemcpyAsync(ctx->d_shadow_list, caller_mask, (size_t)L.n_tiles * sizeof(unsigned long long),
+                               hipMemcpyDeviceToDevice, L.s));
+    svo::AmbientArgs aa;
+    std::memset(&aa, 0, sizeof aa);
+    aa.scratch = ctx->d_shadow_list;
+    for (int k = 0; k < 3; ++k) aa.ambient[k] = ctx->ambient[k];
+    aa.n_rays = ctx->ambient_rays;
+    aa.radius = ctx->ambient_radius;
+    aa.variant = (ctx->ambient_variant + ctx->ambient_step) & 7u;
+    aa.sky = ctx->sky;   // texels null: open rays take the gradient
+    const hipError_t e = svo::launch_ambient(p, aa, L.stack_mode, L.s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("ambient launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
 // The sky pass's input: the launch's tile hit masks.  A caller's own masks are read
 // where they are; so are shadow form 2's and the reflection pass's, which already made the primary launch
 // write them to the head of the shared scratch (their list builds leave the head alone).  Otherwise the
@@ -1529,6 +1568,11 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     if (refl_on && (ctx->options & SVO_OPT_SHADOW_RAYS))
         return fail(SVO_ERR_STATE, "shadow rays with reflection are not supported");
     if (refl_on && lod) return fail(SVO_ERR_STATE, "reflection with LOD is not supported");
+    // ambient term (svo_set_ambient): a pass behind the primary rays and their shadow pass
+    const bool amb_on = ambient_on(ctx) && !out.fetches && !out.starts;
+    if (amb_on && sa) return fail(SVO_ERR_STATE, "svo_render_samples with an ambient term is not supported");
+    if (amb_on && refl_on) return fail(SVO_ERR_STATE, "an ambient term with reflection is not supported");
+    if (amb_on && lod) return fail(SVO_ERR_STATE, "an ambient term with LOD is not supported");
     // skybox (svo_set_skybox): a pass behind the primary rays (and the bounces) that recolours the misses;
     // svo_render_samples blends in its own launch's epilogue, before any pass could run
     const bool sky_on = ctx->sky.texels && !out.fetches && !out.starts;
@@ -1560,6 +1604,11 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     unsigned long long *caller_mask = nullptr;
     if (reflect) {
         rc = reflect_scratch(ctx, L, p, &caller_mask);
+        if (rc) return rc;
+    }
+    const bool ambient = amb_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
+    if (ambient) {
+        rc = ambient_scratch(ctx, L, p, &caller_mask);
         if (rc) return rc;
     }
     // the same for the sky pass: only a launch that writes a colour has one
@@ -1596,6 +1645,10 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     if (rc) return rc;
     if (reflect) {
         rc = reflect_pass(ctx, L, p, caller_mask);
+        if (rc) return rc;
+    }
+    if (ambient) {
+        rc = ambient_pass(ctx, L, p, caller_mask);
         if (rc) return rc;
     }
     if (sky) {
@@ -2144,6 +2197,47 @@ int bounce_device(const void *d_rays, size_t n, uint32_t flags, const void *d_hi
     return SVO_OK;
 }
 
+const char *ambient_setting_error(int n_rays, float radius, uint32_t variant) {
+    if (!svo_ambient::valid_count(n_rays)) return "n_rays must be 4, 8 or 16";
+    if (!(radius > 0.0f)) return "radius must be +inf or finite and positive";
+    if (variant > 7u) return "variant must lie in 0..7";
+    return nullptr;
+}
+
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// The argument checks of svo_ambient_rays(_host) that need no device.
+int check_ambient_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const void *hits, const void *voxel,
+                       int n_rays, float radius, uint32_t variant, const void *rays_out) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!rays) return fail(SVO_ERR_ARG, "null ray list");
+    if (!hits) return fail(SVO_ERR_ARG, "null hit records");
+    if (!voxel) return fail(SVO_ERR_ARG, "null voxel keys");
+    if (!rays_out) return fail(SVO_ERR_ARG, "null output ray list");
+    if (flags & ~(uint32_t)SVO_QUERY_RAW_DIRECTIONS) return fail(SVO_ERR_ARG, "unknown ambient flag bits");
+    if (const char *msg = ambient_setting_error(n_rays, radius, variant)) return fail(SVO_ERR_ARG, msg);
+    if (n > MAX_QUERY_RAYS / (size_t)n_rays) return fail(SVO_ERR_ARG, "more than 2^31 - 1 ambient rays in one batch");
+    const size_t out_bytes = 32 * n * (size_t)n_rays;
+    if (ranges_overlap(rays_out, out_bytes, rays, 32 * n) || ranges_overlap(rays_out, out_bytes, hits, 24 * n) ||
+        ranges_overlap(rays_out, out_bytes, voxel, 8 * n))
+        return fail(SVO_ERR_ARG, "the output ray list overlaps an input");
+    return SVO_OK;
+}
+
+int ambient_device(const void *d_rays, size_t n, uint32_t flags, const void *d_hits, const void *d_voxel, int n_rays,
+                   float radius, uint32_t variant, void *d_rays_out, hipStream_t s) {
+    const hipError_t e = svo::launch_ambient_rays(reinterpret_cast<const svo::QueryRay *>(d_rays), (uint32_t)n,
+                                                  (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u,
+                                                  reinterpret_cast<const svo::Hit *>(d_hits),
+                                                  reinterpret_cast<const unsigned long long *>(d_voxel), n_rays, radius,
+                                                  variant, reinterpret_cast<svo::QueryRay *>(d_rays_out), s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("ambient ray launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
 int check_sky_args(svo_ctx *ctx, const float *dirs, size_t n, const float *rgba) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
     if (!dirs) return fail(SVO_ERR_ARG, "null direction list");
@@ -2284,6 +2378,57 @@ int svo_bounce_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t f
         return SVO_OK;
     } catch (const std::exception &e) {
         return fail(SVO_ERR_HIP, std::string("svo_bounce_rays_host: ") + e.what());
+    }
+}
+
+int svo_ambient_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
+                     const uint64_t *d_voxel, int n_rays, float radius, uint32_t variant, svo_ray *d_rays_out,
+                     void *stream) {
+    int rc = check_ambient_args(ctx, d_rays, n, flags, d_hits, d_voxel, n_rays, radius, variant, d_rays_out);
+    if (rc) return rc;
+    if (((uintptr_t)d_rays | (uintptr_t)d_rays_out) & 15u) return fail(SVO_ERR_ARG, "ray lists must be 16-byte aligned");
+    if (((uintptr_t)d_hits | (uintptr_t)d_voxel) & 7u) return fail(SVO_ERR_ARG, "hit records and voxel keys must be 8-byte aligned");
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        return ambient_device(d_rays, n, flags, d_hits, d_voxel, n_rays, radius, variant, d_rays_out,
+                              stream ? (hipStream_t)stream : c->stream);
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_ambient_rays: ") + e.what());
+    }
+}
+
+int svo_ambient_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
+                          const uint64_t *voxel, int n_rays, float radius, uint32_t variant, svo_ray *rays_out) {
+    int rc = check_ambient_args(ctx, rays, n, flags, hits, voxel, n_rays, radius, variant, rays_out);
+    if (rc) return rc;
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        // staged layout: rays (32 B), hit records (24 B), voxel keys (8 B) per input, then the output rays
+        const size_t off_hits = 32 * n, off_vox = 56 * n, off_out = 64 * n, out_bytes = 32 * n * (size_t)n_rays;
+        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, off_out + out_bytes);
+        if (rc) return rc;
+        rc = order_query_scratch(c, c->stream);
+        if (rc) return rc;
+        char *base = static_cast<char *>(c->q_host);
+        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
+            hipStream_t s;
+            ~Drain() { hipStreamSynchronize(s); }
+        } drain{c->stream};
+        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(base + off_hits, hits, 24 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(base + off_vox, voxel, 8 * n, hipMemcpyHostToDevice, c->stream));
+        rc = ambient_device(base, n, flags, base + off_hits, base + off_vox, n_rays, radius, variant, base + off_out,
+                            c->stream);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(rays_out, base + off_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SVO_OK;
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_ambient_rays_host: ") + e.what());
     }
 }
 
@@ -2611,6 +2756,34 @@ int svo_get_reflection(svo_ctx *ctx, float specular[3], int *max_bounces) {
     return SVO_OK;
 }
 
+int svo_set_ambient(svo_ctx *ctx, const float ambient[3], int n_rays, float radius, uint32_t variant) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    float a[3] = {0.0f, 0.0f, 0.0f};
+    for (int k = 0; k < 3 && ambient; ++k) {
+        if (!(ambient[k] >= 0.0f && ambient[k] <= 4.0f)) return fail(SVO_ERR_ARG, "ambient components must lie in [0, 4]");
+        a[k] = ambient[k];
+    }
+    if (n_rays != 0 && !svo_ambient::valid_count(n_rays)) return fail(SVO_ERR_ARG, "n_rays must be 0, 4, 8 or 16");
+    if (const char *msg = ambient_setting_error(n_rays ? n_rays : 4, radius, variant)) return fail(SVO_ERR_ARG, msg);
+    const bool on = n_rays > 0 && (a[0] != 0.0f || a[1] != 0.0f || a[2] != 0.0f);
+    if (on && is_multi(ctx))
+        return fail(SVO_ERR_STATE, "an ambient term on a multi-device context is not supported");
+    for (int k = 0; k < 3; ++k) ctx->ambient[k] = a[k];
+    ctx->ambient_rays = n_rays;
+    ctx->ambient_radius = radius;
+    ctx->ambient_variant = variant;
+    return SVO_OK;
+}
+
+int svo_get_ambient(svo_ctx *ctx, float ambient[3], int *n_rays, float *radius, uint32_t *variant) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    for (int k = 0; k < 3 && ambient; ++k) ambient[k] = ctx->ambient[k];
+    if (n_rays) *n_rays = ctx->ambient_rays;
+    if (radius) *radius = ctx->ambient_radius;
+    if (variant) *variant = ctx->ambient_variant;
+    return SVO_OK;
+}
+
 int svo_set_skybox(svo_ctx *ctx, const float *rgba, int width, int height, uint32_t flags) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
     if (flags & ~(uint32_t)(SVO_SKY_BILINEAR | SVO_SKY_CLAMP_V)) return fail(SVO_ERR_ARG, "unknown skybox flag bits");
@@ -2864,6 +3037,11 @@ int svo_render_progressive(svo_ctx *ctx, int width, int height, int stack_mode, 
     if (fresh) sample = 0;   // a resized target: this sample replaces the (zeroed) frame
     rc = order_scratch(c, c->stream);
     if (rc) return rc;
+    struct AmbientStep {   // this sample's ambient variant: (variant + sample) & 7, for this launch only
+        svo_ctx *c;
+        ~AmbientStep() { c->ambient_step = 0; }
+    } ambient_step{c};
+    c->ambient_step = sample & 7u;
     svo_frame f{};
     f.rgba = reinterpret_cast<float *>(c->d_out_rgba);   // this sample's Result
     f.layout = SVO_LAYOUT_FRAME;
@@ -2912,6 +3090,11 @@ int svo_render_progressive_async(svo_ctx *ctx, int width, int height, int stack_
     if (rc) return rc;
     rc = order_scratch(c, c->stream);
     if (rc) return rc;
+    struct AmbientStep {   // this sample's ambient variant: (variant + sample) & 7, for this launch only
+        svo_ctx *c;
+        ~AmbientStep() { c->ambient_step = 0; }
+    } ambient_step{c};
+    c->ambient_step = sample & 7u;
     svo_frame f{};
     f.rgba = reinterpret_cast<float *>(c->d_out_rgba);   // this sample's Result
     f.layout = SVO_LAYOUT_FRAME;

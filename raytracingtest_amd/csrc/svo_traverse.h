@@ -274,6 +274,21 @@ struct ReflectArgs {
 };
 hipError_t launch_reflect(const LaunchParams &p, const ReflectArgs &ra, int stack_mode, hipStream_t stream);
 
+// Ambient pass (svo_set_ambient; svo_kernel.hip ambient_list_kernel, svo_ambient.h is the rule), behind a
+// render launch's primary rays and its shadow pass: the hit list as the reflection pass builds it, one wave64
+// per 64 entries, n_rays hemisphere rays each.  p: the launch's own parameters; out.hits and out.voxel hold
+// the primary records (with the shadow pass's bit 3) and keys, the colour outputs among out.rgba / rgba8 /
+// rgb8 are overwritten for the hit pixels.
+struct AmbientArgs {
+    void *scratch;            // shadow_list_bytes, its head the launch's hit masks
+    float ambient[3];
+    int n_rays;               // 4, 8 or 16
+    float radius;             // +inf or > 0, world units
+    uint32_t variant;         // 0 .. 7
+    svo_sky::Texture sky;     // texels non-null: an open ray takes the sky rule, else the gradient
+};
+hipError_t launch_ambient(const LaunchParams &p, const AmbientArgs &aa, int stack_mode, hipStream_t stream);
+
 // Skybox (svo_set_skybox; svo_sky.h is the rule).
 // Sky pass behind a render launch's primary rays (sky_fill_kernel): one wave64 per 8x8 tile of the launch's
 // rows reads the tile's hit mask (masks: svo_frame.hitmask's layout, band-local tiles) as one wave-uniform
@@ -321,5 +336,12 @@ hipError_t launch_query_sort(const uint32_t *keys, uint32_t *keys_out, const uin
 // ray without flag bit 0.  flags: QUERY_RAW.  A flat launch, one thread per ray; out may be rays.
 hipError_t launch_bounce_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
                               const unsigned long long *voxel, QueryRay *out, hipStream_t stream);
+
+// svo_ambient_rays: out[i * n_rays + k] = ray k (svo_ambient.h) of rays[i] and hits[i] / voxel[i], or the
+// dead ray without flag bit 0.  flags: QUERY_RAW.  A flat launch, one thread per output entry; out must
+// not overlap the inputs.
+hipError_t launch_ambient_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
+                               const unsigned long long *voxel, int n_rays, float radius, uint32_t variant, QueryRay *out,
+                               hipStream_t stream);
 
 }  // namespace svo

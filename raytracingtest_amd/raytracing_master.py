@@ -185,6 +185,28 @@ class RaytracingMaster:
         check(_lib.lib().svo_get_reflection(self._ctx, s, ctypes.byref(n)), "svo_get_reflection")
         return (s[0], s[1], s[2]), n.value
 
+    def SetAmbient(self, ambient, n_rays=4, radius=float("inf"), variant=0):
+        """Sky light with ambient occlusion (svo_set_ambient; ambient.ambient_rays is the rule's ray part):
+        per hit pixel n_rays (4, 8 or 16) fixed hemisphere rays leave the voxel face the camera ray entered
+        by; each one that finds nothing within `radius` (world units, inf: unbounded) adds the sky's colour
+        of its direction, and the mean times the albedo times `ambient` (three numbers in [0, 4], None: off,
+        the default) is added to the pixel.  variant (0..7) turns the direction table; RenderProgressive
+        steps it per sample.  Only the colour outputs change."""
+        before = self.GetAmbient()
+        if ambient is None:
+            check(_lib.lib().svo_set_ambient(self._ctx, None, 0, float("inf"), 0), "svo_set_ambient")
+        else:
+            a = (ctypes.c_float * 3)(*[float(v) for v in ambient])
+            check(_lib.lib().svo_set_ambient(self._ctx, a, int(n_rays), float(radius), int(variant)), "svo_set_ambient")
+        if self.GetAmbient() != before:   # another image: the accumulation restarts
+            self.currentSample = 0
+
+    def GetAmbient(self):
+        """((r, g, b) ambient, n_rays, radius, variant) of the context (svo_get_ambient)."""
+        a, n, r, v = (ctypes.c_float * 3)(), ctypes.c_int(), ctypes.c_float(), ctypes.c_uint32()
+        check(_lib.lib().svo_get_ambient(self._ctx, a, ctypes.byref(n), ctypes.byref(r), ctypes.byref(v)), "svo_get_ambient")
+        return (a[0], a[1], a[2]), n.value, r.value, v.value
+
     def SetSkybox(self, texels, bilinear=True, clamp_v=False):
         """~ RayTracingShader.SetTexture(0, "_SkyboxTexture", SkyboxTexture) (RaytracingMaster.cs:28;
         svo_set_skybox): an equirectangular panorama for the rays that leave the scene.  texels: H x W x 4
@@ -502,6 +524,30 @@ class RaytracingMaster:
         results of the batch's trace."""
         check(_lib.lib().svo_bounce_rays(self._ctx, rays_ptr, int(n), self._query_flags(False, raw), hits, voxel, out,
                                          stream), "svo_bounce_rays")
+
+    def AmbientRays(self, rays, hits, voxel, n_rays=4, radius=float("inf"), variant=0, raw=False):
+        """The ambient rays of a traced batch (svo_ambient_rays_host; ambient.ambient_rays is its numpy
+        statement): rays, their hit records and voxel keys as TraceRays returned them; raw: whether the
+        batch was traced with raw=True.  Returns RAY_DTYPE [n * n_rays], entry i * n_rays + k = ray k of
+        rays[i]: dead rays (zero direction, invalid to TraceRays) where there was no hit."""
+        rays = np.ascontiguousarray(rays, _lib.RAY_DTYPE).reshape(-1)
+        hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+        voxel = np.ascontiguousarray(voxel, np.uint64).reshape(-1)
+        if not len(rays) == len(hits) == len(voxel):
+            raise ValueError(f"{len(rays)} rays, {len(hits)} hit records, {len(voxel)} voxel keys")
+        out = np.zeros(len(rays) * max(int(n_rays), 0), _lib.RAY_DTYPE)
+        check(_lib.lib().svo_ambient_rays_host(self._ctx, rays.ctypes.data, len(rays), self._query_flags(False, raw),
+                                               hits.ctypes.data, voxel.ctypes.data, int(n_rays), float(radius),
+                                               int(variant), out.ctypes.data), "svo_ambient_rays_host")
+        return out
+
+    def ambient_rays_device(self, rays_ptr, n, hits, voxel, out, n_rays=4, radius=float("inf"), variant=0, raw=False,
+                            stream=None):
+        """Asynchronous svo_ambient_rays on device buffers: rays_ptr = n svo_ray records, out = n * n_rays
+        (16-byte aligned, no overlap with the inputs), hits (n x 24 bytes) and voxel (n uint64) the
+        results of the batch's trace."""
+        check(_lib.lib().svo_ambient_rays(self._ctx, rays_ptr, int(n), self._query_flags(False, raw), hits, voxel,
+                                          int(n_rays), float(radius), int(variant), out, stream), "svo_ambient_rays")
 
     def beam_starts_device(self, width, height, starts_ptr, band=None, stream=None):
         """svo_beam_starts: every primary ray's beam start (SVO-space t, -inf: the cube entry) into a

@@ -32,6 +32,29 @@ def dead_rays(n):
     return out
 
 
+def entry_face(o, d, hits, voxel):
+    """Steps 1-3 of the rule on traced origins o and directions d ([n, 3] f32), their hit records and
+    voxel keys: (g, out, org) = the entry axis [n], out = d_g > 0 ? -1 : +1 [n] and the origin [n, 3]
+    of a ray that leaves through that face.  Shared with the ambient rule (ambient.py)."""
+    f = np.float32
+    rows = np.arange(len(o))
+    with np.errstate(all="ignore"):
+        side = np.ldexp(f(1.0), hits["hit_scale"].astype(np.int32) - 18).astype(f)[:, None]
+        c = np.stack([(voxel >> np.uint64(21 * k)) & np.uint64(0x1FFFFF) for k in range(3)], axis=1).astype(f)
+        lo = c * side - f(16.0)
+        hi = lo + side
+        face = np.where(d > 0, lo, hi)
+        te = (face - o) * (f(1.0) / d)
+        g = np.zeros(len(o), np.int64)
+        for k in (1, 2):
+            g = np.where(te[:, k] > te[rows, g], k, g)
+        out = np.where(d[rows, g] > 0, f(-1.0), f(1.0)).astype(f)
+        tw = hits["t"] * f(1.0 / 64.0)
+        org = o + tw[:, None] * d
+        org[rows, g] = face[rows, g] + out * (side[:, 0] * f(2.0 ** -6))
+    return g, out, org
+
+
 def bounce_rays(rays, hits, voxel, raw=False):
     """svo_bounce_rays in numpy: out[i] = the bounce ray of rays[i] (RAY_DTYPE) if hits[i]
     (HIT_DTYPE) has flag bit 0, else the dead ray.  voxel: the hits' voxel keys (uint64).
@@ -46,20 +69,8 @@ def bounce_rays(rays, hits, voxel, raw=False):
     o, d = traced["origin"], traced["dir"]
     n = np.stack([hits["nx"], hits["ny"], hits["nz"]], axis=1)
     rows = np.arange(len(rays))
+    g, out, org = entry_face(o, d, hits, voxel)
     with np.errstate(all="ignore"):
-        side = np.ldexp(f(1.0), hits["hit_scale"].astype(np.int32) - 18).astype(f)[:, None]
-        c = np.stack([(voxel >> np.uint64(21 * k)) & np.uint64(0x1FFFFF) for k in range(3)], axis=1).astype(f)
-        lo = c * side - f(16.0)
-        hi = lo + side
-        face = np.where(d > 0, lo, hi)
-        te = (face - o) * (f(1.0) / d)
-        g = np.zeros(len(rays), np.int64)
-        for k in (1, 2):
-            g = np.where(te[:, k] > te[rows, g], k, g)
-        out = np.where(d[rows, g] > 0, f(-1.0), f(1.0)).astype(f)
-        tw = hits["t"] * f(1.0 / 64.0)
-        org = o + tw[:, None] * d
-        org[rows, g] = face[rows, g] + out * (side[:, 0] * f(2.0 ** -6))
         dn = n[:, 0] * d[:, 0]
         dn = dn + n[:, 1] * d[:, 1]
         dn = dn + n[:, 2] * d[:, 2]

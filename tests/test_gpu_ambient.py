@@ -1,0 +1,432 @@
+"""The ambient term on the GPU (svo_ambient_rays, svo_set_ambient): every comparison is byte equality.
+
+References: ambient.ambient_rays (numpy) for the rule's rays, the CPU oracle's orc_intersect_ex on numpy's
+rays for the composition on the query API, and tests/ambient_util.py's expected frame -- the oracle's
+primary frame, numpy's ambient rays, the oracle's trace of each and the fold in numpy f32 -- for renders.
+tests/test_ambient.py pins the rule's header to numpy and shows that these frames are not degenerate."""
+import numpy as np
+import pytest
+
+from raytracingtest_amd import HIT_DTYPE, RaytracingMaster, SvoError
+from raytracingtest_amd import _lib
+from raytracingtest_amd._lib import HIT_INVALID_RAY
+from raytracingtest_amd.ambient import ambient_rays
+from raytracingtest_amd.camera import main_camera
+from raytracingtest_amd.query import apply_t_max, camera_rays
+from raytracingtest_amd.raytracing_master import band_rows
+from raytracingtest_amd.reflection import dead_rays
+from tests import ambient_util as au
+from tests import reflect_util as ru
+from tests import sky_util as su
+from tests.lod_util import pools
+from tests.query_util import MISS, mixed_batch, random_batch
+from tests.test_gpu_reflection import COLOUR_KEYS, FRAME_KEYS, ITEM, PAD, check_frame, colours, dev, render
+
+pytestmark = pytest.mark.gpu
+
+INF = float("inf")
+
+
+@pytest.fixture(scope="module")
+def torch():
+    t = pytest.importorskip("torch")
+    if not t.cuda.is_available():
+        pytest.skip("no GPU")
+    return t
+
+
+@pytest.fixture(scope="module")
+def both(text_svo):
+    return pools(text_svo)
+
+
+@pytest.fixture(scope="module")
+def masters(torch, both):
+    ms = {}
+    for name, svo in both.items():
+        ms[name] = RaytracingMaster(device=0, capacity_nodes=1 << 16)
+        ms[name].SetSVOBuffer(svo)
+    yield ms
+    for m in ms.values():
+        m.close()
+
+
+def want_case(oracle_mod, both, case, mode=0, **kw):
+    pool, (w, h), n_rays, radius, variant = au.CASES[case]
+    return colours(oracle_mod, au.expected_frame(oracle_mod, pool, both[pool], "main", w, h, mode, au.AMBIENT, n_rays, radius,
+                                                 variant, **kw))
+
+
+def set_case(m, case):
+    pool, (w, h), n_rays, radius, variant = au.CASES[case]
+    m.SetAmbient(au.AMBIENT, n_rays, radius, variant)
+    assert m.GetAmbient() == (tuple(float(np.float32(v)) for v in au.AMBIENT), n_rays, radius, variant)
+    return w, h
+
+
+# ---------------------------------------------------------------------------- 1. svo_ambient_rays
+@pytest.mark.parametrize("batch", ["random", "mixed"])
+def test_ambient_rays_equal_numpy(torch, masters, batch):
+    m = masters["text"]
+    rays = random_batch() if batch == "random" else mixed_batch()
+    n = len(rays)
+    assert n == (4133 if batch == "random" else 213)
+    dead = dead_rays(1).tobytes()
+    for raw in (False, True):
+        hits, _, vox = m.TraceRays(rays, raw=raw, want_voxel=True)
+        hit = (hits["flags"] & 1) != 0
+        assert hit.sum() >= (1000 if batch == "random" else 10) and (~hit).sum() >= 30   # both branches are exercised
+        if batch == "mixed":
+            assert ((hits["flags"] & HIT_INVALID_RAY) != 0).sum() >= 100
+        d_rays, d_hits, d_vox = dev(torch, rays), dev(torch, hits), dev(torch, vox)
+        for n_rays, radius in ((4, 1.0), (8, INF), (16, 4.0)):
+            out = torch.empty(((n * n_rays + PAD) * 32,), dtype=torch.uint8, device="cuda")
+            for variant in range(8):
+                want = ambient_rays(rays, hits, vox, n_rays, radius, variant, raw=raw)
+                what = f"{batch} raw {raw} N {n_rays} variant {variant}"
+                if variant == 0:
+                    w2 = want.reshape(n, n_rays)
+                    assert all(w2[i, k].tobytes() == dead for i in np.flatnonzero(~hit)[:40] for k in range(n_rays))
+                    assert not any(w2[i, k].tobytes() == dead for i in np.flatnonzero(hit)[:40] for k in range(n_rays))
+                # the host path
+                got = m.AmbientRays(rays, hits, vox, n_rays, radius, variant, raw=raw)
+                assert got.tobytes() == want.tobytes(), what + ": host path"
+                # the device path into a 0xEE-filled buffer with spare entries
+                out.fill_(0xEE)
+                torch.cuda.synchronize()
+                m.ambient_rays_device(d_rays.data_ptr(), n, d_hits.data_ptr(), d_vox.data_ptr(), out.data_ptr(), n_rays, radius,
+                                      variant, raw=raw)
+                m.synchronize()
+                a = out.cpu().numpy()
+                assert np.all(a[n * n_rays * 32:] == 0xEE), what + ": written past n * n_rays entries"
+                assert a[:n * n_rays * 32].tobytes() == want.tobytes(), what + ": device path"
+        assert d_rays.cpu().numpy().tobytes() == rays.tobytes()
+        assert d_hits.cpu().numpy().tobytes() == hits.tobytes() and d_vox.cpu().numpy().tobytes() == vox.tobytes()
+    out.fill_(0xEE)
+    torch.cuda.synchronize()
+    m.ambient_rays_device(d_rays.data_ptr(), 0, d_hits.data_ptr(), d_vox.data_ptr(), out.data_ptr(), 4, 1.0, 0)   # n = 0: nothing
+    m.synchronize()
+    assert bool((out == 0xEE).all())
+    assert len(m.AmbientRays(rays[:0], hits[:0], vox[:0], 4, 1.0, 0)) == 0
+    with pytest.raises(SvoError, match=r"\(-1\).*overlap"):
+        m.ambient_rays_device(out.data_ptr(), n, d_hits.data_ptr(), d_vox.data_ptr(), out.data_ptr() + 32, 4, 1.0, 0)
+
+
+# ---------------------------------------------------------------------------- 2. composition on the query API
+def test_composition_on_the_query_api(torch, oracle_mod, both, masters):
+    """svo_trace_rays(raw) -> svo_ambient_rays(N = 4, radius 1) -> svo_trace_rays on the device from the camera
+    rays of Text / Main / 200 x 120: the rays are numpy's, the records the oracle's after the t_max filter."""
+    m, (w, h) = masters["text"], ru.SIZES["raster"]
+    n, n_rays = w * h, 4
+    c2w, inv_proj = main_camera().uniforms(w, h)
+    tr = au.traced(oracle_mod, "text", both["text"], "main", w, h, 0, n_rays, 1.0, 0)
+    prim = tr["prim"]
+    d_rays = dev(torch, camera_rays(c2w, inv_proj, w, h))
+    d_hits = torch.zeros(n * 24, dtype=torch.uint8, device="cuda")
+    d_vox = torch.zeros(n * 8, dtype=torch.uint8, device="cuda")
+    d_amb = torch.full((n * n_rays * 32,), 0xEE, dtype=torch.uint8, device="cuda")
+    d_hits2 = torch.zeros(n * n_rays * 24, dtype=torch.uint8, device="cuda")
+    torch.cuda.synchronize()
+    m.trace_rays_device(d_rays.data_ptr(), n, hits=d_hits.data_ptr(), voxel=d_vox.data_ptr(), raw=True)
+    m.ambient_rays_device(d_rays.data_ptr(), n, d_hits.data_ptr(), d_vox.data_ptr(), d_amb.data_ptr(), n_rays, 1.0, 0, raw=True)
+    m.trace_rays_device(d_amb.data_ptr(), n * n_rays, hits=d_hits2.data_ptr())
+    m.synchronize()
+    assert d_hits.cpu().numpy().tobytes() == prim["hits"].tobytes(), "the primary rays"
+    want_rays = dead_rays(n * n_rays).reshape(n, n_rays)
+    want_rays[prim["px"]] = tr["rays"].reshape(-1, n_rays)
+    assert d_amb.cpu().numpy().tobytes() == want_rays.tobytes(), "the ambient rays"
+    want_hits = np.repeat(MISS, n * n_rays).reshape(n, n_rays)
+    want_hits["flags"] = HIT_INVALID_RAY
+    filtered = tr["hits"].copy()
+    cut = ((filtered["flags"] & 1) != 0) & ~apply_t_max(filtered, tr["rays"]["t_max"])
+    filtered[cut] = MISS   # the t_max filter: a miss record with no flags
+    assert cut.sum() >= 1000   # the radius does cut hits
+    want_hits[prim["px"]] = filtered.reshape(-1, n_rays)
+    got = d_hits2.cpu().numpy().view(HIT_DTYPE)
+    bad = np.flatnonzero((got.view(np.uint8).reshape(-1, 24) != want_hits.reshape(-1).view(np.uint8).reshape(-1, 24)).any(axis=1))
+    assert len(bad) == 0, f"{len(bad)} records differ, first {bad[:8].tolist()}"
+    is_open = (got["flags"] & (1 | HIT_INVALID_RAY)) == 0
+    assert is_open.reshape(n, n_rays)[prim["px"]].tobytes() == tr["open"].tobytes()
+
+
+# ---------------------------------------------------------------------------- 3. render parity
+@pytest.mark.parametrize("case", list(au.CASES))
+def test_render_equals_the_expected_frame(torch, oracle_mod, both, masters, case):
+    """rgba, rgba8, rgb8 are the builder's; hits, compact, position, voxel and hitmask the bytes of an
+    ambient-off render.  Both stack modes on the first case of each pool."""
+    pool = au.CASES[case][0]
+    m = masters[pool]
+    try:
+        m.SetAmbient(None)
+        w, h = au.CASES[case][1]
+        m.UpdateShaderParameters(main_camera(), w, h)
+        for mode in ((0, 1) if case in ("text_raster", "tree7_raster") else (0,)):
+            m.SetAmbient(None)
+            off = render(torch, m, w, h, mode)
+            prim = ru.primary(oracle_mod, pool, both[pool], "main", w, h, mode)
+            assert off["hits"].tobytes() == prim["hits"].tobytes() and off["rgba"].tobytes() == prim["rgba"].tobytes()
+            set_case(m, case)
+            want = want_case(oracle_mod, both, case, mode)
+            if pool == "tree7":
+                assert want["rgba"].tobytes() != prim["rgba"].tobytes()
+            for launch in range(2):
+                check_frame(render(torch, m, w, h, mode), want, off, f"{case} mode {mode} launch {launch}")
+    finally:
+        m.SetAmbient(None)
+
+
+@pytest.mark.parametrize("case", ["text_raster", "tree7_strips"])
+def test_entry_points_give_the_same_frame(torch, oracle_mod, both, case):
+    """A caller that passes rgba8 only (hits, keys and masks are then scratch), svo_render, a caller's own
+    hitmask, records without colours, a caller stream, a band in both layouts."""
+    pool = au.CASES[case][0]
+    svo = both[pool]
+    want = want_case(oracle_mod, both, case)
+    m = RaytracingMaster(device=0, capacity_nodes=1 << 16)
+    try:
+        m.SetSVOBuffer(svo)
+        w, h = au.CASES[case][1]
+        n = w * h
+        m.UpdateShaderParameters(main_camera(), w, h)
+        off = render(torch, m, w, h)
+        set_case(m, case)
+        got = render(torch, m, w, h, keys=("rgba8",))   # a fresh context: every input of the pass is scratch
+        assert got["rgba8"].tobytes() == want["rgba8"].tobytes(), "rgba8 alone"
+        got = render(torch, m, w, h, keys=("rgb8",))
+        assert got["rgb8"].tobytes() == want["rgb8"].tobytes(), "rgb8 alone"
+        rgba, hits = m.Render(w, h)
+        assert rgba.tobytes() == want["rgba"].tobytes() and hits.tobytes() == off["hits"].tobytes(), "svo_render"
+        rgba, _ = m.Render(w, h, want_hits=False)
+        assert rgba.tobytes() == want["rgba"].tobytes(), "svo_render without hits"
+        check_frame(render(torch, m, w, h, keys=("rgba", "hitmask")), want, off, "rgba + hitmask")
+        check_frame(render(torch, m, w, h, keys=("compact", "rgba")), want, off, "compact + rgba")
+        check_frame(render(torch, m, w, h, keys=("hits", "voxel")), want, off, "hits + voxel: no pass")
+        s = torch.cuda.Stream()
+        check_frame(render(torch, m, w, h, stream=s), want, off, "caller stream")
+        m.forget_stream(s.cuda_stream)
+        tiles_x = (w + 7) // 8
+        full = {k: np.zeros(n * ITEM[k], np.uint8) for k in ITEM}
+        full["hitmask"] = np.zeros(tiles_x * ((h + 7) // 8) * 8, np.uint8)
+        for rank in range(2):
+            band = (8, rank, 2)
+            rows = band_rows(h, band)
+            part = render(torch, m, w, h, band=band)
+            for k in ITEM:
+                full[k].reshape(h, -1)[rows] = part[k].reshape(len(rows), -1)
+            full["hitmask"].reshape(h // 8, -1)[rows[::8] // 8] = part["hitmask"].reshape(len(rows) // 8, -1)
+        check_frame(full, want, off, "band layout")
+        into = {k: torch.full((len(full[k]),), 0xEE, dtype=torch.uint8, device="cuda") for k in ITEM}
+        for rank in range(2):
+            got = render(torch, m, w, h, band=(8, rank, 2), layout=_lib.LAYOUT_FRAME, into=into)
+        check_frame(got, want, off, "frame layout")
+    finally:
+        m.close()
+
+
+def test_render_on_a_guarded_pool(torch, oracle_mod):
+    """The cyclic pool of tests/guard_pools.py takes the guarded loop (trace_lean<MODE, GUARD = true>) in the
+    pass as in the primary launch; an ambient ray that ends on the overflow rule is open."""
+    from raytracingtest_amd.svo_data import SVOData
+    from tests import guard_pools as gp
+    nodes, att = gp.cyclic7()
+    svo = SVOData(nodes=nodes, attachments=att)
+    w, h = gp.W, gp.H
+    m = RaytracingMaster(device=0, capacity_nodes=1 << 10)
+    try:
+        m.SetSVOBuffer(svo)
+        m.UpdateShaderParameters(gp.diagonal_camera(), w, h)
+        for mode in (0, 1):
+            m.SetAmbient(None)
+            off = render(torch, m, w, h, mode)
+            tr = au.traced(oracle_mod, "cyclic7", svo, "diagonal", w, h, mode, 4, INF, 1)
+            overflowed = (tr["hits"]["flags"] & gp.FLAG_OVERFLOW) != 0
+            occluded = (tr["hits"]["flags"] & 1) != 0
+            print("cyclic7 mode", mode, "ambient rays", len(tr["rays"]), "overflowed", int(overflowed.sum()), "occluded",
+                  int(occluded.sum()))
+            assert len(tr["prim"]["px"]) >= 1000 and overflowed.sum() >= 1
+            assert tr["open"].reshape(-1)[overflowed & ~occluded].all()   # the overflow rule: a miss, so open
+            m.SetAmbient(au.AMBIENT, 4, INF, 1)
+            want = colours(oracle_mod, au.expected_frame(oracle_mod, "cyclic7", svo, "diagonal", w, h, mode, au.AMBIENT, 4, INF, 1))
+            check_frame(render(torch, m, w, h, mode), want, off, f"cyclic7 mode {mode}")
+    finally:
+        m.close()
+
+
+# ---------------------------------------------------------------------------- 4. with SVO_OPT_SHADOW_RAYS
+@pytest.mark.parametrize("case", ["text_raster", "tree7_raster"])
+def test_with_shadow_rays(torch, oracle_mod, both, case):
+    """Under all three shadow forms the pass runs behind the shadow pass and reads bit 3 from the record: the
+    three frames are identical bytes and equal the expected frame; bit 3 is still in hits and compact."""
+    pool = au.CASES[case][0]
+    w, h = au.CASES[case][1]
+    want = want_case(oracle_mod, both, case, shadows=True)
+    ref = ru.primary(oracle_mod, pool, both[pool], "main", w, h, oracle_mod.SHADOW_RAYS)
+    assert ((ref["hits"]["flags"] & 8) != 0).sum() >= 100
+    frames = []
+    for form in (_lib.SHADOW_FUSED, _lib.SHADOW_TILES, _lib.SHADOW_LIST):
+        m = RaytracingMaster(device=0, capacity_nodes=1 << 16, config={"shadow_form": form})
+        try:
+            m.SetSVOBuffer(both[pool])
+            m.UpdateShaderParameters(main_camera(), w, h)
+            m.SetShadowRays(True)
+            off = render(torch, m, w, h)
+            assert off["hits"].tobytes() == ref["hits"].tobytes() and off["rgba"].tobytes() == ref["rgba"].tobytes()
+            set_case(m, case)
+            got = render(torch, m, w, h)
+            check_frame(got, want, off, f"{case} shadow form {form}")
+            assert ((got["hits"].view(HIT_DTYPE)["flags"] & 8) != 0).sum() >= 100
+            assert ((got["compact"].view(np.uint32).reshape(-1, 3)[:, 1] >> 16) & 8 != 0).sum() >= 100
+            for keys in (("rgba8",), ("compact", "rgba"), ("rgba", "hitmask")):
+                check_frame(render(torch, m, w, h, keys=keys), want, off, f"{case} shadow form {form} {keys}")
+            frames.append(got)
+        finally:
+            m.close()
+    for k in FRAME_KEYS:
+        assert frames[0][k].tobytes() == frames[1][k].tobytes() == frames[2][k].tobytes(), k
+
+
+# ---------------------------------------------------------------------------- 5. with a skybox
+@pytest.mark.parametrize("bilinear", [False, True])
+def test_with_a_skybox(torch, oracle_mod, both, masters, bilinear):
+    """A 16 x 8 random texture on tree7 with radius inf: open rays take sky.py's rule on their direction, miss
+    pixels the sky pass's colour."""
+    m = masters["tree7"]
+    pool, (w, h), n_rays, radius, variant = au.CASES["tree7_raster"]
+    tex = su.texture(16, 8)
+    try:
+        m.UpdateShaderParameters(main_camera(), w, h)
+        m.SetAmbient(None)
+        m.SetSkybox(None)
+        off = render(torch, m, w, h)
+        want = want_case(oracle_mod, both, "tree7_raster", texture=(tex, bilinear, False))
+        gradient = want_case(oracle_mod, both, "tree7_raster")
+        hit = (off["hits"].view(HIT_DTYPE)["flags"] & 1) != 0
+        assert (want["rgba"][hit] != gradient["rgba"][hit]).any(axis=1).mean() >= 0.5   # the texture shows in the hits
+        assert (want["rgba"][~hit] != gradient["rgba"][~hit]).any(axis=1).all()
+        m.SetSkybox(tex, bilinear=bilinear, clamp_v=False)
+        set_case(m, "tree7_raster")
+        for keys in (FRAME_KEYS, ("rgba8",)):
+            check_frame(render(torch, m, w, h, keys=keys), want, off, f"skybox bilinear {bilinear} {keys}")
+    finally:
+        m.SetSkybox(None)
+        m.SetAmbient(None)
+
+
+# ---------------------------------------------------------------------------- 6. progressive
+def test_progressive_steps_the_variant(torch, oracle_mod, both):
+    """Three RenderProgressive samples use variants (v + s) & 7: the accumulation is oracle.accumulate folded
+    over the three expected frames."""
+    pool, (w, h), n_rays, radius, _ = au.CASES["tree7_raster"]
+    svo, v0 = both[pool], 6
+    m = RaytracingMaster(device=0, capacity_nodes=1 << 16)
+    try:
+        m.SetSVOBuffer(svo)
+        m.SetAmbient(au.AMBIENT, n_rays, radius, v0)
+        acc = np.zeros((w * h, 4), np.float32)
+        frames = []
+        for s, px_off in enumerate(((0.5, 0.5), (0.25, 0.75), (0.75, 0.25))):
+            m.UpdateShaderParameters(main_camera(), w, h, pixel_offset=px_off)
+            m.currentSample = s
+            words, prog = m.RenderProgressive(w, h, want_rgba8=True, want_rgba=True)
+            frame = au.expected_frame(oracle_mod, pool, svo, "main", w, h, 0, au.AMBIENT, n_rays, radius, (v0 + s) & 7, off=px_off)
+            frames.append(frame)
+            oracle_mod.accumulate(acc, np.ascontiguousarray(frame), s)
+            assert prog.tobytes() == acc.tobytes(), f"progressive sample {s}"
+            assert words.tobytes() == oracle_mod.pack_rgba8(acc).tobytes(), f"progressive sample {s}: display words"
+        same_variant = au.expected_frame(oracle_mod, pool, svo, "main", w, h, 0, au.AMBIENT, n_rays, radius, v0, off=(0.25, 0.75))
+        assert same_variant.tobytes() != frames[1].tobytes()   # the step is visible in the expectation
+        # a plain render afterwards uses the setting's own variant again
+        m.UpdateShaderParameters(main_camera(), w, h)
+        rgba, _ = m.Render(w, h)
+        want = au.expected_frame(oracle_mod, pool, svo, "main", w, h, 0, au.AMBIENT, n_rays, radius, v0)
+        assert rgba.tobytes() == want.tobytes()
+    finally:
+        m.close()
+
+
+# ---------------------------------------------------------------------------- 7. isolation
+def test_off_is_off(torch, both):
+    """Off, on, off: the first and third renders are identical in every output; NULL and n_rays 0 are off; the
+    kernel-timing records still count the primary kernel only."""
+    pool, (w, h), n_rays, radius, variant = au.CASES["tree7_strips"]
+    rays = random_batch()
+    m = RaytracingMaster(device=0, capacity_nodes=1 << 16)
+    try:
+        m.SetSVOBuffer(both[pool])
+        m.UpdateShaderParameters(main_camera(), w, h)
+        assert m.GetAmbient() == ((0.0, 0.0, 0.0), 0, INF, 0)
+        before = [render(torch, m, w, h) for _ in range(2)][1]
+        q_before = m.TraceRays(rays, want_position=True, want_voxel=True)
+        m.SetAmbient(au.AMBIENT, n_rays, radius, variant)
+        on = render(torch, m, w, h)
+        assert on["rgba"].tobytes() != before["rgba"].tobytes() and on["hits"].tobytes() == before["hits"].tobytes()
+        for amb, n in ((None, 0), ((0.0, 0.0, 0.0), 8), (au.AMBIENT, 0)):
+            if amb is None:
+                m.SetAmbient(None)
+            else:
+                m.SetAmbient(amb, n, radius, variant)
+            after = render(torch, m, w, h)
+            for k in FRAME_KEYS:
+                assert after[k].tobytes() == before[k].tobytes(), f"{amb} / {n}: {k}"
+        q_after = m.TraceRays(rays, want_position=True, want_voxel=True)
+        assert all(a.tobytes() == b.tobytes() for a, b in zip(q_before, q_after))
+        m.set_kernel_timing(True)
+        m.stage_time(_lib.STAGE_KERNEL)
+        m.SetAmbient(au.AMBIENT, n_rays, radius, variant)
+        for _ in range(3):
+            render(torch, m, w, h, keys=COLOUR_KEYS)
+        ms, count = m.stage_time(_lib.STAGE_KERNEL)
+        assert count == 3 and ms > 0.0
+    finally:
+        m.close()
+
+
+# ---------------------------------------------------------------------------- 8. refusals
+def test_stated_limits_are_state_errors(torch, both):
+    svo, (w, h) = both["tree7"], ru.SIZES["raster"]
+    n = w * h
+    m = RaytracingMaster(device=0, capacity_nodes=1 << 16)
+    m2 = RaytracingMaster(devices=[0, 0], capacity_nodes=1 << 16)
+    try:
+        m.SetSVOBuffer(svo)
+        m.UpdateShaderParameters(main_camera(), w, h)
+        m.SetAmbient(au.AMBIENT, 4, INF, 0)
+        b = {"hits": torch.full((n * 24,), 0xEE, dtype=torch.uint8, device="cuda"),
+             "rgba": torch.full((n * 16,), 0xEE, dtype=torch.uint8, device="cuda")}
+        torch.cuda.synchronize()
+        ptrs = {k: v.data_ptr() for k, v in b.items()}
+
+        def refused(match):
+            with pytest.raises(SvoError, match=r"\(-5\).*" + match):
+                m.render_frame(w, h, **ptrs)
+            with pytest.raises(SvoError, match=r"\(-5\)"):
+                m.render_device(w, h, rgba_ptr=ptrs["rgba"], hits_ptr=ptrs["hits"])
+            with pytest.raises(SvoError, match=r"\(-5\)"):
+                m.Render(w, h)
+            with pytest.raises(SvoError, match=r"\(-5\)"):
+                m.RenderProgressive(w, h)
+        m.SetReflection(*ru.DEFAULT)
+        refused("ambient term with reflection")
+        m.SetReflection(None)
+        m.SetLod(0.01, 0.0)
+        refused("ambient term with LOD")
+        m.SetLod(0.0, 0.0)
+        for offs in ([(0.5, 0.5)], [(0.5, 0.5), (0.25, 0.75)]):
+            with pytest.raises(SvoError, match=r"\(-5\).*svo_render_samples with an ambient term"):
+                m.render_samples(w, h, offs, 0, ptrs["rgba"])
+        m.synchronize()
+        torch.cuda.synchronize()
+        assert all(bool((v == 0xEE).all()) for v in b.values()), "an output was written"
+        m.render_frame(w, h, **ptrs)   # the ambient term alone renders
+        m.synchronize()
+        # a multi-device context: a non-off setting is refused, off is accepted
+        m2.SetSVOBuffer(svo)
+        with pytest.raises(SvoError, match=r"\(-5\).*multi-device"):
+            m2.SetAmbient(au.AMBIENT, 4, INF, 0)
+        m2.SetAmbient(None)
+        m2.SetAmbient((0.0, 0.0, 0.0), 8, 2.0, 3)
+        assert m2.GetAmbient() == ((0.0, 0.0, 0.0), 8, 2.0, 3)
+        m2.SetAmbient(au.AMBIENT, 0, INF, 0)
+    finally:
+        m.close()
+        m2.close()

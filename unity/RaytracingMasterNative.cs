@@ -98,6 +98,18 @@ public static class SvoNative {
                                                                    [Out] SvoRay[] raysOut);
     [DllImport(Lib)] public static extern int svo_set_reflection(IntPtr ctx, [In] float[] specular, int maxBounces);
     [DllImport(Lib)] public static extern int svo_get_reflection(IntPtr ctx, [Out] float[] specular, out int maxBounces);
+    // Ambient (svo_rt.h): sky light with ambient occlusion -- the renders' setting and the ray queries' building block
+    public const int AmbientMaxRays = 16;
+    [DllImport(Lib)] public static extern int svo_set_ambient(IntPtr ctx, [In] float[] ambient, int nRays, float radius,
+                                                              uint variant);
+    [DllImport(Lib)] public static extern int svo_get_ambient(IntPtr ctx, [Out] float[] ambient, out int nRays,
+                                                              out float radius, out uint variant);
+    [DllImport(Lib)] public static extern int svo_ambient_rays(IntPtr ctx, IntPtr dRays, UIntPtr n, uint flags, IntPtr dHits,
+                                                               IntPtr dVoxel, int nRays, float radius, uint variant,
+                                                               IntPtr dRaysOut, IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_ambient_rays_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr n, uint flags,
+                                                                    [In] SvoHit[] hits, [In] ulong[] voxel, int nRays,
+                                                                    float radius, uint variant, [Out] SvoRay[] raysOut);
     // Skybox (svo_rt.h): the reference's _SkyboxTexture for rays that leave the scene, and its rule for ray queries
     public const uint SkyBilinear = 1, SkyClampV = 2;
     [DllImport(Lib)] public static extern int svo_set_skybox(IntPtr ctx, [In] Color[] rgba, int width, int height, uint flags);
@@ -165,6 +177,17 @@ public class RaytracingMasterNative : MonoBehaviour {
     [Range(0,7)] public int maxBounces;
     Vector3 _specularSet;
     int _maxBouncesSet = 0;
+    // Ambient (svo_set_ambient; it changes the image; the reference has none): per hit pixel ambientRays (0 = off,
+    // 4, 8 or 16) hemisphere rays about the voxel face; each one that finds nothing within ambientRadius world
+    // units (0 = unbounded) adds the sky of its direction, and the mean times the albedo times `ambient` (per
+    // channel in [0, 4]) is added.  The accumulation turns the direction table per sample.  Not supported together
+    // with specular, lodPixels or gpus > 1.
+    public Vector3 ambient;
+    [Range(0, 16)] public int ambientRays;
+    public float ambientRadius = 0;
+    Vector3 _ambientSet;
+    int _ambientRaysSet = 0;
+    float _ambientRadiusSet = 0;
     // Skybox (svo_set_skybox; it changes the image): the reference's SkyboxTexture (RaytracingMaster.cs:6), an
     // equirectangular panorama (readable, at most 8192 x 8192), uploaded once when the context is created as the
     // reference binds it once in Awake (:28).  None: the procedural gradient.  Not supported with gpus > 1.
@@ -337,6 +360,12 @@ public class RaytracingMasterNative : MonoBehaviour {
                         "svo_set_reflection");
         if (specular != _specularSet || maxBounces != _maxBouncesSet) {   // another image as well
             _specularSet = specular; _maxBouncesSet = maxBounces; _currentSample = 0;
+        }
+        SvoNative.Check(SvoNative.svo_set_ambient(_ctx, new[] { ambient.x, ambient.y, ambient.z }, ambientRays,
+                                                  ambientRadius > 0f ? ambientRadius : float.PositiveInfinity, 0u),
+                        "svo_set_ambient");
+        if (ambient != _ambientSet || ambientRays != _ambientRaysSet || ambientRadius != _ambientRadiusSet) {   // and here
+            _ambientSet = ambient; _ambientRaysSet = ambientRays; _ambientRadiusSet = ambientRadius; _currentSample = 0;
         }
         // the pipelined path moves 3-byte pixels (RGB24: a quarter fewer bytes over PCIe); `pipelined`
         // is an Inspector field, so a toggle at run time recreates the texture in the other format
