@@ -76,7 +76,11 @@ typedef struct svo_hit_compact {
  * a weighted deal (0 < cycle <= 256) gives band b to rank owner[b % cycle]
  * (owner: `cycle` entries, each < band_count), e.g. fewer bands to the display
  * rank, which also assembles the frame.  A rank's output holds only its own rows,
- * in increasing y.  {1, 0, 1} (or NULL) = whole frame. */
+ * in increasing y.  {1, 0, 1} (or NULL) = whole frame.  band_rows is any positive
+ * number, not only a multiple of the 8-row tile (the kernels' tiles are cut from the
+ * rank's own rows in order, so one tile may hold rows of several bands), and a rank may
+ * own no rows at all (a band taller than the frame): its render is a no-op that returns
+ * SVO_OK and its part may be empty (0 bytes; a sparse part: the 4-byte count, 0). */
 typedef struct svo_band {
     int band_rows;
     int band_rank;
@@ -185,7 +189,9 @@ int svo_create(int device, size_t capacity_nodes, svo_ctx **out);
  * member's payload over xGMI when hipDeviceCanAccessPeer allows it; when it does
  * not (or svo_config.peer_copy forces it), the member's stream copies the payload
  * into a buffer on the display device (hipMemcpyPeerAsync) and the assemble
- * reads that copy -- creation no longer fails for lack of peer access. */
+ * reads that copy -- creation no longer fails for lack of peer access.
+ * band_rows need not be a multiple of the 8-row tile, and a member may own no rows
+ * of a frame (its render is a no-op and its payload is empty). */
 int svo_create_multi(const int *devices, int num_devices, size_t capacity_nodes, int band_rows, svo_ctx **out);
 int svo_num_devices(svo_ctx *ctx, int *num_devices);
 /* How member `index`'s band payload reaches the display device: SVO_LINK_SELF

@@ -2750,8 +2750,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void tile_scan_local_kernel(const uns
         total += v;
     }
     if (i < n) local[i] = before + incl - c;
-    if (tid == 0) sums[blockIdx.x] = total;
-    if (n == 0 && tid == 0) *count = 0u;   // an empty band: no pack workgroup writes it
+    // an empty band (a rank without rows) has no chunk: its part is the 4-byte count alone
+    // (SVO_SPARSE_PART_BYTES(0, 0)), so no chunk total is stored behind it
+    if (tid == 0 && n > 0) sums[blockIdx.x] = total;
+    if (n == 0 && tid == 0) *count = 0u;   // no pack workgroup writes it
 }
 
 // INDEX: pack the hit pixels' band-local indices (lr * width + x, 4 bytes) instead of

@@ -15,9 +15,11 @@ from raytracingtest_amd.camera import main_camera, main_light, overview_camera
 from raytracingtest_amd.query import make_rays, sanitize_rays
 from raytracingtest_amd.reflection import bounce_rays
 from tests.guard_pools import diagonal_camera
+from tests.split_cases import edge_camera
 
 CAMS = {"main": main_camera, "overview": overview_camera}
-POSES = dict(CAMS, diagonal=diagonal_camera)   # diagonal: the guarded pools' camera (tests/guard_pools.py)
+# diagonal: the guarded pools' camera (tests/guard_pools.py); edge: the split tests' (tests/split_cases.py)
+POSES = dict(CAMS, diagonal=diagonal_camera, edge=edge_camera)
 SIZES = {"raster": (200, 120), "strips": (256, 128)}   # 25 tile columns: the raster path; 32: XCD strips
 DEFAULT = ((0.5, 0.25, 0.75), 7)
 SECOND = ((1.0, 0.0, 0.0), 2)
