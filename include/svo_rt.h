@@ -47,7 +47,15 @@ typedef enum svo_status {
 } svo_status;
 
 /* Stack modes: HLSL reproduces the float2 round trip
- * of NVIDIASVO.compute:98; EXACT keeps exact (parent, t_max) entries. */
+ * of NVIDIASVO.compute:98; EXACT keeps exact (parent, t_max) entries.  The round
+ * trip keeps 24 bits of each entry: a parent index above 2^24 is rounded, and a
+ * popped t_max (asint ~ 2^30) is off by up to 2^-17 relative, which hides a voxel
+ * whose crossing is shorter than 2^-17 t (t in SVO units from the ray's origin):
+ * voxels of a pool 16 or more levels deep are lost when seen from outside the
+ * cube (1 of 1,000 aimed rays at depth 16, 8 % at depth 19, 20 % at depth 21;
+ * none from origins next to the geometry).  Hosts take EXACT when the node count
+ * exceeds 2^24 or the pool's depth is 16 or more (INTEGRATION.md "Stack mode",
+ * tests/test_geometry_model.py). */
 typedef enum svo_stack_mode { SVO_STACK_HLSL = 0, SVO_STACK_EXACT = 1 } svo_stack_mode;
 
 /* Per-pixel hit record, 24 bytes. */

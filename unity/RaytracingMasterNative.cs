@@ -138,7 +138,9 @@ public static class SvoNative {
     // (SURVEY.md Appendix A): such pools (C4, C5) trace with the exact stack
     public static int StackModeFor(IntPtr ctx) {
         Check(svo_get_info(ctx, out UIntPtr n, out int depth, out int device), "svo_get_info");
-        return (ulong)n > (1UL << 24) ? StackExact : StackHlsl;
+        // parents above 2^24 are rounded by the HLSL stack, and so is a popped t_max (2^-17 relative): pools of
+        // 16 levels and more lose voxels seen from outside the cube (INTEGRATION.md "Stack mode")
+        return (ulong)n > (1UL << 24) || depth >= 16 ? StackExact : StackHlsl;
     }
 
     // Unity Matrix4x4 is column-major in memory (m00, m10, m20, m30, m01, ...), which is the C-ABI order.
