@@ -725,6 +725,120 @@ __device__ __forceinline__ size_t out_index(const LaunchParams &p, int lr, int g
     return (size_t)(p.out.frame_layout ? gy : lr) * (size_t)p.width + (size_t)x;
 }
 
+// ------------------------------------- the frame of a pass behind the primary launch
+// DESIGN.md 3.2f.  A pass reads the primary launch's records back, traces further rays with the
+// primary rays' loop and rewrites what changed, with plain stores at the render's own addresses.
+// A list pass runs one wave64 per 64 entries of the compacted hit list (pack_hits_kernel<INDEX>,
+// tile order) over a grid that covers every pixel, with the primary kernel's [slot][lane] LDS stack.
+
+// The finished ray (org, dir), world space, through the lean loop.  All lanes of a wave start
+// together, so the wave-uniform trip count (*trips) is each tracing lane's own iteration count.
+// The caller's exec mask must not be empty (the loop's lane masks come from it).
+template <int MODE, bool GUARD, bool FA, bool LOD = false>
+__device__ __forceinline__ Ray traced_ray(const LaunchParams &p, const float org[3], const float dir[3],
+                                          uint2 *__restrict__ stk, int *trips = nullptr) {
+    Ray r;
+    setup_ray(org, dir, r);
+    FRay f;
+    to_fray(r, f);
+    trace_lean<MODE, GUARD, false, FA, false, LOD>(p, f, stk);
+    from_fray(f, r);
+    if (trips) *trips = f.trips;
+    return r;
+}
+
+// A shadow ray's walk: the guard is a runtime test here (two instantiations per stack mode).
+template <int MODE, bool FA>
+__device__ __forceinline__ Ray traced_shadow_ray(const LaunchParams &p, const float org[3], const float dir[3],
+                                                 uint2 *__restrict__ stk, int *trips = nullptr) {
+    if (p.guard) return traced_ray<MODE, true, false>(p, org, dir, stk, trips);
+    return traced_ray<MODE, false, FA>(p, org, dir, stk, trips);
+}
+
+// This lane's entry of a list pass.  false: the whole wave lies past the device-side count and
+// leaves.  Lanes past the count in the last wave stay (mine false, pixel 0) for the wave-uniform loops.
+struct ListEntry {
+    bool mine;
+    int x, lr, gy;
+    size_t i;      // out_index
+};
+__device__ __forceinline__ bool list_entry(const LaunchParams &p, const uint32_t *__restrict__ list,
+                                           const uint32_t *__restrict__ count, ListEntry &e) {
+    const uint32_t k = blockIdx.x * TILE + threadIdx.x;
+    const uint32_t n = *count;
+    if (blockIdx.x * TILE >= n) return false;
+    e.mine = k < n;
+    const uint32_t px = e.mine ? list[k] : 0u;
+    e.x = (int)(px % (uint32_t)p.width);
+    e.lr = (int)(px / (uint32_t)p.width);
+    e.gy = global_row(p, e.lr);
+    e.i = out_index(p, e.lr, e.gy, e.x);
+    return true;
+}
+
+// The shadow passes' read of the primary record at i: words 1 and 2 and the normal, from out.hits or
+// from out.compact plus the attachment (fetched only when the hit bit is set: a miss has no parent).
+__device__ __forceinline__ void primary_record(const LaunchParams &p, size_t i, uint32_t &w1, uint32_t &w2, float n[3]) {
+    if (p.out.hits) {
+        const uint2 *rec = reinterpret_cast<const uint2 *>(p.out.hits + i);
+        const uint2 a = rec[0], b = rec[1], c = rec[2];
+        w1 = a.y; w2 = b.x;
+        n[0] = __uint_as_float(b.y); n[1] = __uint_as_float(c.x); n[2] = __uint_as_float(c.y);
+    } else {
+        const uint3 c = reinterpret_cast<const uint3 *>(p.out.compact)[i];
+        w1 = c.y; w2 = c.z;
+        if ((w1 >> 16) & 1u) {
+            const uint2 a = p.att[c.x];
+            decode_normal(a.y >> 16, n);
+            normalize3(n);
+        }
+    }
+}
+
+// The colour passes' read of a hit pixel's record (out.hits): t, normal, scale, the albedo, and the
+// primary colour recomputed from the record as assemble_kernel does -- black with flag bit 3, the
+// shadow pass's mark (never set under reflection: svo_rt.hip refuses it with shadow rays).
+__device__ __forceinline__ void primary_colour(const LaunchParams &p, size_t i, float &t, float nrm[3], int &scale,
+                                               float alb[3], float rgb[3]) {
+    const uint2 *rec = reinterpret_cast<const uint2 *>(p.out.hits + i);
+    const uint2 h0 = rec[0], h1 = rec[1], h2 = rec[2];
+    t = __uint_as_float(h1.x);
+    nrm[0] = __uint_as_float(h1.y); nrm[1] = __uint_as_float(h2.x); nrm[2] = __uint_as_float(h2.y);
+    scale = (int)((h0.y >> 8) & 0xFFu);
+    const uint2 a = p.att[h0.x];
+    decode_dxt(a.x, a.y, (int)(h0.y & 0xFFu), alb);
+    rgb[0] = rgb[1] = rgb[2] = 0.0f;
+    if (!((h0.y >> 16) & 8u)) shade_hit(p.cam, nrm, alb, rgb);
+}
+
+// An occluded pixel: flag bit 3 in the record and a black Result (R:109-111) in every output.
+__device__ __forceinline__ void mark_occluded(const Outputs &out, size_t i, uint32_t w1) {
+    const uint32_t nw1 = w1 | (8u << 16);
+    if (out.hits) reinterpret_cast<uint32_t *>(out.hits + i)[1] = nw1;
+    if (out.compact) out.compact[3 * i + 1] = nw1;
+    if (out.rgba) out.rgba[i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    if (out.rgba8) out.rgba8[i] = 255u << 24;
+    if (out.rgb8) {
+        uint8_t *d = out.rgb8 + 3 * i;
+        d[0] = d[1] = d[2] = 0;
+    }
+}
+
+// A pixel's new colour in every colour output (rgb8: three byte stores, the record is 3 bytes apart).
+__device__ __forceinline__ void store_colour(const Outputs &out, size_t i, const float rgb[3]) {
+    if (out.rgba) out.rgba[i] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
+    if (out.rgba8 || out.rgb8) {
+        const uint32_t w = pack_rgba8(rgb[0], rgb[1], rgb[2]);
+        if (out.rgba8) out.rgba8[i] = w;
+        if (out.rgb8) {
+            uint8_t *d = out.rgb8 + 3 * i;
+            d[0] = (uint8_t)w;
+            d[1] = (uint8_t)(w >> 8);
+            d[2] = (uint8_t)(w >> 16);
+        }
+    }
+}
+
 // ------------------------------------------------------------- segmented rays
 // One ray's traversal split into K t-segments that run side by side (VERDICT r4 item 1:
 // a heavy tile's wave is a serial chain of up to ~270 trips that bounds a frame split over N
@@ -1487,61 +1601,28 @@ __global__ __launch_bounds__(TILE) void shadow_tile_kernel(LaunchParams p, int t
     const size_t i = out_index(p, lr, gy, x);
     uint32_t w1 = 0, w2 = 0;
     float n[3] = {0.0f, 0.0f, 0.0f};
-    if (inside) {
-        if (p.out.hits) {
-            const uint2 *rec = reinterpret_cast<const uint2 *>(p.out.hits + i);
-            const uint2 a = rec[0], b = rec[1], c = rec[2];
-            w1 = a.y; w2 = b.x;
-            n[0] = __uint_as_float(b.y); n[1] = __uint_as_float(c.x); n[2] = __uint_as_float(c.y);
-        } else {
-            const uint3 c = reinterpret_cast<const uint3 *>(p.out.compact)[i];
-            w1 = c.y; w2 = c.z;
-            if ((w1 >> 16) & 1u) {
-                const uint2 a = p.att[c.x];
-                decode_normal(a.y >> 16, n);
-                normalize3(n);
-            }
-        }
-    }
+    if (inside) primary_record(p, i, w1, w2, n);
     const bool hit = (w1 >> 16) & 1u;
     const bool any_hit = __ballot(hit) != 0;   // whole wave, before any lane leaves
     if (p.shadow_cost && lane == 0 && !any_hit) p.shadow_cost[t] = 0;
     if (!hit) return;
     float so[3], sd[3];
     shadow_ray(p, x, gy, w2, __float_as_uint(n[0]), __float_as_uint(n[1]), __float_as_uint(n[2]), so, sd);
-    Ray r;
-    setup_ray(so, sd, r);
-    uint2 *stk = stk_base + lane;
-    FRay f;   // the primary rays' lean loop (one wave of shadow rays per tile, parallel directions)
-    to_fray(r, f);
-    if (p.guard) trace_lean<MODE, true>(p, f, stk);
-    else trace_lean<MODE, false, false, FA>(p, f, stk);
-    from_fray(f, r);
-    if (p.shadow_cost) p.shadow_cost[t] = (uint16_t)min(f.trips, 65535);   // same value from every tracing lane
-    if (r.scale < S_MAX) {   // occluded
-        const uint32_t nw1 = w1 | (8u << 16);
-        if (p.out.hits) reinterpret_cast<uint32_t *>(p.out.hits + i)[1] = nw1;
-        if (p.out.compact) p.out.compact[3 * i + 1] = nw1;
-        if (p.out.rgba) p.out.rgba[i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-        if (p.out.rgba8) p.out.rgba8[i] = 255u << 24;
-        if (p.out.rgb8) {
-            uint8_t *d = p.out.rgb8 + 3 * i;
-            d[0] = d[1] = d[2] = 0;
-        }
-    }
+    // the primary rays' lean loop (one wave of shadow rays per tile, parallel directions)
+    int trips;
+    const Ray r = traced_shadow_ray<MODE, FA>(p, so, sd, stk_base + lane, &trips);
+    if (p.shadow_cost) p.shadow_cost[t] = (uint16_t)min(trips, 65535);   // same value from every tracing lane
+    if (r.scale < S_MAX) mark_occluded(p.out, i, w1);
 }
 
-// Compacted form (svo_config.shadow_form 2): the primary pass's
-// hit masks are scanned and its hit pixels packed into a dense list in tile order
-// (pack_hits_kernel<INDEX>, the sparse payload's ballot + prefix sum), and one wave
-// traces 64 consecutive list entries.  The grid covers every pixel; waves past the
-// device-side hit count return at once.
+// Compacted form (svo_config.shadow_form 2): the list-pass frame, one shadow
+// ray per entry.  Lanes past the count leave one by one (the pass has no wave-uniform loop), so the entry
+// is read here and not through list_entry, which cost this kernel 12 SGPRs (46 -> 58).
 template <int MODE, bool FA = false>
 __global__ __launch_bounds__(TILE) void shadow_list_kernel(LaunchParams p, const uint32_t *__restrict__ list,
                                                            const uint32_t *__restrict__ count) {
     extern __shared__ uint2 stk_base[];
-    const int lane = (int)threadIdx.x;
-    const uint32_t k = blockIdx.x * TILE + (uint32_t)lane;
+    const uint32_t k = blockIdx.x * TILE + threadIdx.x;
     const uint32_t n = *count;
     if (blockIdx.x * TILE >= n || k >= n) return;
     const uint32_t px = list[k];
@@ -1549,40 +1630,12 @@ __global__ __launch_bounds__(TILE) void shadow_list_kernel(LaunchParams p, const
     const int gy = global_row(p, lr);
     const size_t i = out_index(p, lr, gy, x);
     uint32_t w1, w2;
-    float nrm[3];
-    if (p.out.hits) {
-        const uint2 *rec = reinterpret_cast<const uint2 *>(p.out.hits + i);
-        const uint2 a = rec[0], b = rec[1], c = rec[2];
-        w1 = a.y; w2 = b.x;
-        nrm[0] = __uint_as_float(b.y); nrm[1] = __uint_as_float(c.x); nrm[2] = __uint_as_float(c.y);
-    } else {
-        const uint3 c = reinterpret_cast<const uint3 *>(p.out.compact)[i];
-        w1 = c.y; w2 = c.z;
-        const uint2 a = p.att[c.x];
-        decode_normal(a.y >> 16, nrm);
-        normalize3(nrm);
-    }
+    float nrm[3] = {0.0f, 0.0f, 0.0f};
+    primary_record(p, i, w1, w2, nrm);   // every entry is a hit
     float so[3], sd[3];
     shadow_ray(p, x, gy, w2, __float_as_uint(nrm[0]), __float_as_uint(nrm[1]), __float_as_uint(nrm[2]), so, sd);
-    Ray r;
-    setup_ray(so, sd, r);
-    uint2 *stk = stk_base + lane;
-    FRay f;
-    to_fray(r, f);
-    if (p.guard) trace_lean<MODE, true>(p, f, stk);
-    else trace_lean<MODE, false, false, FA>(p, f, stk);
-    from_fray(f, r);
-    if (r.scale < S_MAX) {   // occluded
-        const uint32_t nw1 = w1 | (8u << 16);
-        if (p.out.hits) reinterpret_cast<uint32_t *>(p.out.hits + i)[1] = nw1;
-        if (p.out.compact) p.out.compact[3 * i + 1] = nw1;
-        if (p.out.rgba) p.out.rgba[i] = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-        if (p.out.rgba8) p.out.rgba8[i] = 255u << 24;
-        if (p.out.rgb8) {
-            uint8_t *d = p.out.rgb8 + 3 * i;
-            d[0] = d[1] = d[2] = 0;
-        }
-    }
+    const Ray r = traced_shadow_ray<MODE, FA>(p, so, sd, stk_base + threadIdx.x);
+    if (r.scale < S_MAX) mark_occluded(p.out, i, w1);
 }
 
 // -------------------------------------------------------------- ray queries
@@ -1652,13 +1705,7 @@ __device__ __forceinline__ void query_rays_body(const LaunchParams &p, const Que
         if (!any_valid && lane == 0 && q.out.hitmask && !q.index) q.out.hitmask[blockIdx.x] = 0ull;
         return;
     }
-    Ray r;
-    setup_ray(org, dir, r);
-    uint2 *stk = stk_base + lane;
-    FRay f;
-    to_fray(r, f);
-    trace_lean<MODE, GUARD, false, FA, false, LOD>(p, f, stk);
-    from_fray(f, r);
+    const Ray r = traced_ray<MODE, GUARD, FA, LOD>(p, org, dir, stk_base + lane);
     record(p, r, 0, 0, o);   // p.out is empty: the hit words only (position and key below)
     bool hit = r.scale < S_MAX;
     if (hit && !(__uint_as_float(o.w[2]) * (1.0f / 64.0f) <= t_lim)) {
@@ -1744,10 +1791,8 @@ __global__ __launch_bounds__(256) void bounce_rays_kernel(const QueryRay *rays, 
 
 // ------------------------------------------------------- reflection pass
 // svo_set_reflection: the reference's bounce loop (R:159-166) with specular != 0, as a
-// second pass over the primary launch's compacted hit list -- shadow_list_kernel's shape, one wave per
-// 64 list entries.  A lane starts from its pixel's camera ray and primary record (out.hits, out.voxel)
-// with res = the primary colour, recomputed from the record as assemble_kernel does, and e = 1; then
-// per bounce: e *= specular (all zero: the path ends), the bounce ray of the current ray and hit
+// pass in the list-pass frame.  A lane starts from its pixel's camera ray and primary record (out.hits,
+// out.voxel) with res = the primary colour and e = 1; then per bounce: e *= specular (all zero: the path ends), the bounce ray of the current ray and hit
 // (svo_reflect.h), classified and clamped as a query's ray (invalid: the path ends), traced with the
 // primary rays' loop, res += e * (shade_hit of the new hit | sky of the traced direction); a miss ends
 // the path.  The wave loops while any lane's path is alive: trace_lean runs under `if (alive)` only
@@ -1762,34 +1807,21 @@ __device__ __forceinline__ void reflect_list_body(const LaunchParams p, const ui
                                                   const uint32_t *__restrict__ count, float sr, float sg, float sb,
                                                   int max_bounces, const svo_sky::Texture &tex) {
     extern __shared__ uint2 stk_base[];
-    const int lane = (int)threadIdx.x;
-    const uint32_t k = blockIdx.x * TILE + (uint32_t)lane;
-    const uint32_t n = *count;
-    if (blockIdx.x * TILE >= n) return;   // the whole wave
-    const bool mine = k < n;
-    const uint32_t px = mine ? list[k] : 0u;
-    const int x = (int)(px % (uint32_t)p.width), lr = (int)(px / (uint32_t)p.width);
-    const int gy = global_row(p, lr);
-    const size_t i = out_index(p, lr, gy, x);
+    ListEntry le;
+    if (!list_entry(p, list, count, le)) return;
+    const bool mine = le.mine;
     float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f}, nrm[3] = {0.0f, 0.0f, 0.0f};
     float res[3] = {0.0f, 0.0f, 0.0f}, e[3] = {1.0f, 1.0f, 1.0f}, t = 0.0f;
     int scale = 0;
     unsigned long long key = 0ull;
     if (mine) {
-        const uint2 *rec = reinterpret_cast<const uint2 *>(p.out.hits + i);
-        const uint2 h0 = rec[0], h1 = rec[1], h2 = rec[2];
-        t = __uint_as_float(h1.x);
-        nrm[0] = __uint_as_float(h1.y); nrm[1] = __uint_as_float(h2.x); nrm[2] = __uint_as_float(h2.y);
-        scale = (int)((h0.y >> 8) & 0xFFu);
-        key = p.out.voxel[i];
-        camera_ray(p.cam, p.width, p.height, x, gy, o, d);
-        const uint2 a = p.att[h0.x];
         float alb[3];
-        decode_dxt(a.x, a.y, (int)(h0.y & 0xFFu), alb);
-        shade_hit(p.cam, nrm, alb, res);
+        primary_colour(p, le.i, t, nrm, scale, alb, res);
+        key = p.out.voxel[le.i];
+        camera_ray(p.cam, p.width, p.height, le.x, le.gy, o, d);
     }
     bool alive = mine;
-    uint2 *stk = stk_base + lane;
+    uint2 *stk = stk_base + threadIdx.x;
 #pragma nounroll
     for (int b = 1; b <= max_bounces; ++b) {
         if (alive) {
@@ -1806,12 +1838,7 @@ __device__ __forceinline__ void reflect_list_body(const LaunchParams p, const ui
         }
         if (LM_OF(alive) == 0) break;   // wave-uniform
         if (alive) {
-            Ray r;
-            setup_ray(o, d, r);
-            FRay f;
-            to_fray(r, f);
-            trace_lean<MODE, GUARD, false, FA>(p, f, stk);
-            from_fray(f, r);
+            const Ray r = traced_ray<MODE, GUARD, FA>(p, o, d, stk);
             float col[3];
             const bool hit = r.scale < S_MAX;
             if (hit) {
@@ -1839,18 +1866,7 @@ __device__ __forceinline__ void reflect_list_body(const LaunchParams p, const ui
             alive = hit;
         }
     }
-    if (!mine) return;
-    if (p.out.rgba) p.out.rgba[i] = make_float4(res[0], res[1], res[2], 1.0f);
-    if (p.out.rgba8 || p.out.rgb8) {
-        const uint32_t w = pack_rgba8(res[0], res[1], res[2]);
-        if (p.out.rgba8) p.out.rgba8[i] = w;
-        if (p.out.rgb8) {
-            uint8_t *dst = p.out.rgb8 + 3 * i;
-            dst[0] = (uint8_t)w;
-            dst[1] = (uint8_t)(w >> 8);
-            dst[2] = (uint8_t)(w >> 16);
-        }
-    }
+    if (mine) store_colour(p.out, le.i, res);
 }
 
 template <int MODE, bool GUARD, bool FA>
@@ -1892,11 +1908,9 @@ __global__ __launch_bounds__(256) void ambient_rays_kernel(const QueryRay *__res
     dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
 }
 
-// svo_set_ambient: sky light with ambient occlusion, as one more pass over the primary
-// launch's compacted hit list -- reflect_list_kernel's shape, one wave per 64 list entries, the same
-// [slot][lane] LDS stack.  A lane starts from its pixel's camera ray and primary record (out.hits,
-// out.voxel): direct = the ambient-off colour recomputed from the record (black with flag bit 3, the
-// shadow pass's mark), and the entry face of the voxel (svo_reflect.h entry_face) gives the common origin
+// svo_set_ambient: sky light with ambient occlusion, in the list-pass frame.  A lane
+// starts from its pixel's camera ray and primary record (out.hits, out.voxel): direct = the primary
+// colour, and the entry face of the voxel (svo_reflect.h entry_face) gives the common origin
 // of its n_rays rays.  The k loop is outermost and wave-uniform: all lanes trace table entry k together
 // (svo_ambient.h ambient_dir, the entry read through a scalar load), as a query traces {origin, radius,
 // dir, 0} with flags 0: classify (only the origin can fail it), the clamp (the identity on a table
@@ -1911,41 +1925,32 @@ __device__ __forceinline__ void ambient_list_body(const LaunchParams p, const ui
                                                   int n_rays, float radius, uint32_t variant,
                                                   const svo_sky::Texture &tex) {
     extern __shared__ uint2 stk_base[];
-    const int lane = (int)threadIdx.x;
-    const uint32_t k = blockIdx.x * TILE + (uint32_t)lane;
-    const uint32_t n = *count;
-    if (blockIdx.x * TILE >= n) return;   // the whole wave
-    const bool mine = k < n;
-    const uint32_t px = mine ? list[k] : 0u;
-    const int x = (int)(px % (uint32_t)p.width), lr = (int)(px / (uint32_t)p.width);
-    const int gy = global_row(p, lr);
-    const size_t i = out_index(p, lr, gy, x);
+    ListEntry le;
+    if (!list_entry(p, list, count, le)) return;
+    const bool mine = le.mine;
     float org[3] = {0.0f, 0.0f, 0.0f}, res[3] = {0.0f, 0.0f, 0.0f}, w[3] = {0.0f, 0.0f, 0.0f};
     float out = 1.0f;
     int g = 0;
     bool go = false;
     if (mine) {
-        const uint2 *rec = reinterpret_cast<const uint2 *>(p.out.hits + i);
-        const uint2 h0 = rec[0], h1 = rec[1], h2 = rec[2];
-        const float nrm[3] = {__uint_as_float(h1.y), __uint_as_float(h2.x), __uint_as_float(h2.y)};
-        float o[3], d[3];
-        camera_ray(p.cam, p.width, p.height, x, gy, o, d);
-        const uint2 a = p.att[h0.x];
-        float alb[3];
-        decode_dxt(a.x, a.y, (int)(h0.y & 0xFFu), alb);
-        if (!((h0.y >> 16) & 8u)) shade_hit(p.cam, nrm, alb, res);
+        float t, nrm[3], alb[3], o[3], d[3];
+        int scale;
+        primary_colour(p, le.i, t, nrm, scale, alb, res);
+        camera_ray(p.cam, p.width, p.height, le.x, le.gy, o, d);
         w[0] = ar * alb[0]; w[1] = ag * alb[1]; w[2] = ab * alb[2];
-        g = svo_reflect::entry_face(o, d, __uint_as_float(h1.x), (int)((h0.y >> 8) & 0xFFu), p.out.voxel[i], org, &out);
+        g = svo_reflect::entry_face(o, d, t, scale, p.out.voxel[le.i], org, &out);
         go = finite_f32(org[0]) && finite_f32(org[1]) && finite_f32(org[2]);   // the query's classify
     }
     float S[3] = {0.0f, 0.0f, 0.0f};
-    uint2 *stk = stk_base + lane;
+    uint2 *stk = stk_base + threadIdx.x;
     if (LM_OF(go) != 0) {   // wave-uniform
 #pragma nounroll
         for (int kk = 0; kk < n_rays; ++kk) {
             if (go) {
                 float dir[3];
                 svo_ambient::ambient_dir(n_rays, kk, variant, g, out, dir);
+                // written out, not traced_ray: through the wrapper the trip loop's schedule changed (a select
+                // moved behind the loop's lgkmcnt wait) and the N = 4 frame measured 2 % slower
                 Ray r;
                 setup_ray(org, dir, r);
                 FRay f;
@@ -1973,17 +1978,7 @@ __device__ __forceinline__ void ambient_list_body(const LaunchParams p, const ui
     res[0] = res[0] + w[0] * (S[0] * inv_n);
     res[1] = res[1] + w[1] * (S[1] * inv_n);
     res[2] = res[2] + w[2] * (S[2] * inv_n);
-    if (p.out.rgba) p.out.rgba[i] = make_float4(res[0], res[1], res[2], 1.0f);
-    if (p.out.rgba8 || p.out.rgb8) {
-        const uint32_t c = pack_rgba8(res[0], res[1], res[2]);
-        if (p.out.rgba8) p.out.rgba8[i] = c;
-        if (p.out.rgb8) {
-            uint8_t *dst = p.out.rgb8 + 3 * i;
-            dst[0] = (uint8_t)c;
-            dst[1] = (uint8_t)(c >> 8);
-            dst[2] = (uint8_t)(c >> 16);
-        }
-    }
+    store_colour(p.out, le.i, res);
 }
 
 struct AmbientKernelArgs {   // one kernel argument beside LaunchParams (which does not grow)
@@ -2032,17 +2027,7 @@ __global__ __launch_bounds__(TILE) void sky_fill_kernel(LaunchParams p, svo_sky:
     float org[3], dir[3], rgb[3];
     camera_ray(p.cam, p.width, p.height, x, gy, org, dir);
     svo_sky::sample(tex, dir, rgb);
-    if (p.out.rgba) p.out.rgba[i] = make_float4(rgb[0], rgb[1], rgb[2], 1.0f);
-    if (p.out.rgba8 || p.out.rgb8) {
-        const uint32_t w = pack_rgba8(rgb[0], rgb[1], rgb[2]);
-        if (p.out.rgba8) p.out.rgba8[i] = w;
-        if (p.out.rgb8) {
-            uint8_t *dst = p.out.rgb8 + 3 * i;
-            dst[0] = (uint8_t)w;
-            dst[1] = (uint8_t)(w >> 8);
-            dst[2] = (uint8_t)(w >> 16);
-        }
-    }
+    store_colour(p.out, i, rgb);
 }
 
 // svo_sample_sky: one thread per direction; a thread reads its own entry before it writes its own slot, so
@@ -2166,6 +2151,22 @@ static size_t lds_pad() {
     return pad;
 }
 
+// The lean loop of a query or a pass behind the primary launch, as compile-time constants:
+// f(MODE, GUARD, FA) gets three std::integral_constants.  A guarded pool takes the guarded loop, which
+// has no fetch-all form: FA = fetch_all && !guard.  (The shadow kernels test the guard at run time and
+// take MODE and FA only.)
+template <class F>
+static hipError_t with_loop(const LaunchParams &p, int stack_mode, F &&f) {
+    const auto with_mode = [&](auto mode) {
+        if (p.guard) f(mode, std::true_type{}, std::false_type{});
+        else if (p.fetch_all) f(mode, std::false_type{}, std::true_type{});
+        else f(mode, std::false_type{}, std::false_type{});
+    };
+    if (stack_mode == 0) with_mode(std::integral_constant<int, 0>{});
+    else with_mode(std::integral_constant<int, 1>{});
+    return hipGetLastError();
+}
+
 template <int MODE, bool COUNT>
 static hipError_t launch_variant(const LaunchParams &p, hipStream_t stream) {
     const int bx = (p.width + 7) / 8, by = (p.local_rows + 7) / 8;
@@ -2229,35 +2230,18 @@ static hipError_t launch_variant(const LaunchParams &p, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------- ray queries
-template <int MODE>
-static hipError_t launch_query_mode(const LaunchParams &p, const QueryArgs &q, hipStream_t stream) {
-    const size_t lds = (size_t)p.slots * TILE * sizeof(uint2) + lds_pad();
-    const dim3 grid((q.n + (uint32_t)TILE - 1u) / (uint32_t)TILE), block(TILE);
-    if (p.lod) {
-        if (p.guard)
-            hipLaunchKernelGGL((query_rays_lod_kernel<MODE, true, false>), grid, block, lds, stream, p, q);
-        else if (p.fetch_all)
-            hipLaunchKernelGGL((query_rays_lod_kernel<MODE, false, true>), grid, block, lds, stream, p, q);
-        else
-            hipLaunchKernelGGL((query_rays_lod_kernel<MODE, false, false>), grid, block, lds, stream, p, q);
-        return hipGetLastError();
-    }
-    if (p.guard)
-        hipLaunchKernelGGL((query_rays_kernel<MODE, true, false>), grid, block, lds, stream, p, q);
-    else if (p.fetch_all)
-        hipLaunchKernelGGL((query_rays_kernel<MODE, false, true>), grid, block, lds, stream, p, q);
-    else
-        hipLaunchKernelGGL((query_rays_kernel<MODE, false, false>), grid, block, lds, stream, p, q);
-    return hipGetLastError();
-}
-
 hipError_t launch_query(const LaunchParams &p, const QueryArgs &q, int stack_mode, hipStream_t stream) {
     if (q.n == 0) return hipSuccess;
     if (q.index && q.out.hitmask) {   // ordered: hit lanes or their bits in
         const hipError_t e = hipMemsetAsync(q.out.hitmask, 0, (((size_t)q.n + 63) / 64) * sizeof(unsigned long long), stream);
         if (e != hipSuccess) return e;
     }
-    return stack_mode == 0 ? launch_query_mode<0>(p, q, stream) : launch_query_mode<1>(p, q, stream);
+    const size_t lds = (size_t)p.slots * TILE * sizeof(uint2) + lds_pad();
+    const dim3 grid((q.n + (uint32_t)TILE - 1u) / (uint32_t)TILE), block(TILE);
+    return with_loop(p, stack_mode, [&](auto M, auto G, auto FA) {
+        if (p.lod) hipLaunchKernelGGL((query_rays_lod_kernel<M(), G(), FA()>), grid, block, lds, stream, p, q);
+        else hipLaunchKernelGGL((query_rays_kernel<M(), G(), FA()>), grid, block, lds, stream, p, q);
+    });
 }
 
 hipError_t launch_query_keys(const QueryArgs &q, uint32_t *keys, uint32_t *index, hipStream_t stream) {
@@ -2829,6 +2813,30 @@ size_t shadow_list_bytes(int width, int local_rows) {
     return sparse_layout(n, width * local_rows, 4).scratch + 4 * (size_t)n + 4 * (size_t)((n + SCAN_THREADS - 1) / SCAN_THREADS);
 }
 
+// A list pass's launch: the hit list, packed behind the hit masks at the head of `scratch` (the same
+// masks give the same list, so a second pass rebuilds it), its device-side count, a grid that covers
+// every pixel, the stack's LDS, and the launch's parameters with no hit-mask output.
+struct HitList {
+    const uint32_t *list, *cnt;
+    dim3 grid;
+    size_t lds;
+    LaunchParams q;
+};
+static hipError_t pack_hit_list(const LaunchParams &p, void *scratch, hipStream_t stream, HitList &h) {
+    const hipError_t e = launch_pack<true>(nullptr, p.width, p.local_rows, scratch, stream);
+    if (e != hipSuccess) return e;
+    const int n = ((p.width + 7) / 8) * ((p.local_rows + 7) / 8);
+    const SparseLayout L = sparse_layout(n, p.width * p.local_rows, 4);
+    const uint8_t *base = reinterpret_cast<const uint8_t *>(scratch);
+    h.list = reinterpret_cast<const uint32_t *>(base + L.rgb);
+    h.cnt = reinterpret_cast<const uint32_t *>(base + L.offsets) + n;
+    h.grid = dim3((unsigned)(((size_t)p.width * (size_t)p.local_rows + TILE - 1) / TILE));
+    h.lds = (size_t)p.slots * TILE * sizeof(uint2);
+    h.q = p;
+    h.q.out.hitmask = nullptr;
+    return hipSuccess;
+}
+
 hipError_t launch_assemble(const AssembleParams &a, hipStream_t stream) {
     if (a.width <= 0 || a.height <= 0) return hipSuccess;
     if ((a.part_format == PART_RGBA8 || a.part_format == PART_RGB8 || a.part_format == PART_SPARSE_RGB8) &&
@@ -3059,15 +3067,12 @@ hipError_t launch_beam_splat(const BeamParams &b, hipStream_t stream) {
     return hipGetLastError();
 }
 
-template <int MODE>
-static hipError_t launch_shadows(const LaunchParams &p, hipStream_t stream) {
+static hipError_t launch_shadows(const LaunchParams &p, int stack_mode, hipStream_t stream) {
     const int bx = (p.width + 7) / 8, by = (p.local_rows + 7) / 8;
     const size_t lds = (size_t)p.slots * TILE * sizeof(uint2);
-    if (p.fetch_all && !p.guard)
-        hipLaunchKernelGGL((shadow_tile_kernel<MODE, true>), dim3((unsigned)(bx * by)), dim3(TILE), lds, stream, p, bx);
-    else
-        hipLaunchKernelGGL((shadow_tile_kernel<MODE>), dim3((unsigned)(bx * by)), dim3(TILE), lds, stream, p, bx);
-    return hipGetLastError();
+    return with_loop(p, stack_mode, [&](auto M, auto, auto FA) {
+        hipLaunchKernelGGL((shadow_tile_kernel<M(), FA()>), dim3((unsigned)(bx * by)), dim3(TILE), lds, stream, p, bx);
+    });
 }
 
 // svo_beam_starts (diagnostics): every pixel's primary-ray start under the launch's beam starts --
@@ -3104,115 +3109,54 @@ hipError_t launch_render(const LaunchParams &p, int stack_mode, hipStream_t stre
     if (e != hipSuccess) return e;
     if (primary_end && (e = hipEventRecord(primary_end, stream)) != hipSuccess) return e;
     if (!count && p.shadows == 1 && (p.out.hits || p.out.compact))
-        return stack_mode == 0 ? launch_shadows<0>(p, stream) : launch_shadows<1>(p, stream);
+        return launch_shadows(p, stack_mode, stream);
     if (!count && p.shadows == 3 && (p.out.hits || p.out.compact) && p.out.hitmask) {
         // compacted shadow pass: the hit list in the scratch whose head the primary filled
-        if ((e = launch_pack<true>(nullptr, p.width, p.local_rows, p.out.hitmask, stream)) != hipSuccess) return e;
-        const int n = ((p.width + 7) / 8) * ((p.local_rows + 7) / 8);
-        const SparseLayout L = sparse_layout(n, p.width * p.local_rows, 4);
-        const uint8_t *base = reinterpret_cast<const uint8_t *>(p.out.hitmask);
-        const uint32_t *list = reinterpret_cast<const uint32_t *>(base + L.rgb);
-        const uint32_t *cnt = reinterpret_cast<const uint32_t *>(base + L.offsets) + n;
-        const size_t lds = (size_t)p.slots * TILE * sizeof(uint2);
-        const dim3 grid((unsigned)(((size_t)p.width * (size_t)p.local_rows + TILE - 1) / TILE));
-        LaunchParams q = p;
-        q.out.hitmask = nullptr;
-        if (stack_mode == 0) {
-            if (p.fetch_all && !p.guard) hipLaunchKernelGGL((shadow_list_kernel<0, true>), grid, dim3(TILE), lds, stream, q, list, cnt);
-            else hipLaunchKernelGGL((shadow_list_kernel<0>), grid, dim3(TILE), lds, stream, q, list, cnt);
-        } else {
-            if (p.fetch_all && !p.guard) hipLaunchKernelGGL((shadow_list_kernel<1, true>), grid, dim3(TILE), lds, stream, q, list, cnt);
-            else hipLaunchKernelGGL((shadow_list_kernel<1>), grid, dim3(TILE), lds, stream, q, list, cnt);
-        }
-        return hipGetLastError();
+        HitList h;
+        if ((e = pack_hit_list(p, p.out.hitmask, stream, h)) != hipSuccess) return e;
+        return with_loop(p, stack_mode, [&](auto M, auto, auto FA) {
+            hipLaunchKernelGGL((shadow_list_kernel<M(), FA()>), h.grid, dim3(TILE), h.lds, stream, h.q, h.list, h.cnt);
+        });
     }
     return hipSuccess;
-}
-
-template <int MODE>
-static hipError_t launch_reflect_mode(const LaunchParams &q, const uint32_t *list, const uint32_t *cnt, const ReflectArgs &ra,
-                                      hipStream_t stream) {
-    const size_t lds = (size_t)q.slots * TILE * sizeof(uint2);
-    const dim3 grid((unsigned)(((size_t)q.width * (size_t)q.local_rows + TILE - 1) / TILE)), block(TILE);
-    const float sr = ra.specular[0], sg = ra.specular[1], sb = ra.specular[2];
-    // guarded pools and fetch_all select the loop as shadow_list_kernel does
-    if (ra.sky.texels) {
-        if (q.guard)
-            hipLaunchKernelGGL((reflect_list_sky_kernel<MODE, true, false>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces, ra.sky);
-        else if (q.fetch_all)
-            hipLaunchKernelGGL((reflect_list_sky_kernel<MODE, false, true>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces, ra.sky);
-        else
-            hipLaunchKernelGGL((reflect_list_sky_kernel<MODE, false, false>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces, ra.sky);
-    }
-    else if (q.guard)
-        hipLaunchKernelGGL((reflect_list_kernel<MODE, true, false>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces);
-    else if (q.fetch_all)
-        hipLaunchKernelGGL((reflect_list_kernel<MODE, false, true>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces);
-    else
-        hipLaunchKernelGGL((reflect_list_kernel<MODE, false, false>), grid, block, lds, stream, q, list, cnt, sr, sg, sb, ra.max_bounces);
-    return hipGetLastError();
 }
 
 hipError_t launch_reflect(const LaunchParams &p, const ReflectArgs &ra, int stack_mode, hipStream_t stream) {
     if (!p.out.hits || !p.out.voxel || !ra.scratch || ra.max_bounces < 1 || p.width <= 0 || p.local_rows <= 0)
         return hipErrorInvalidValue;
-    // the hit list in the scratch whose head holds the launch's hit masks
-    hipError_t e = launch_pack<true>(nullptr, p.width, p.local_rows, ra.scratch, stream);
+    HitList h;
+    const hipError_t e = pack_hit_list(p, ra.scratch, stream, h);
     if (e != hipSuccess) return e;
-    const int n = ((p.width + 7) / 8) * ((p.local_rows + 7) / 8);
-    const SparseLayout L = sparse_layout(n, p.width * p.local_rows, 4);
-    const uint8_t *base = reinterpret_cast<const uint8_t *>(ra.scratch);
-    const uint32_t *list = reinterpret_cast<const uint32_t *>(base + L.rgb);
-    const uint32_t *cnt = reinterpret_cast<const uint32_t *>(base + L.offsets) + n;
-    LaunchParams q = p;
-    q.out.hitmask = nullptr;
-    return stack_mode == 0 ? launch_reflect_mode<0>(q, list, cnt, ra, stream) : launch_reflect_mode<1>(q, list, cnt, ra, stream);
-}
-
-template <int MODE>
-static hipError_t launch_ambient_mode(const LaunchParams &q, const uint32_t *list, const uint32_t *cnt, const AmbientArgs &aa,
-                                      hipStream_t stream) {
-    const size_t lds = (size_t)q.slots * TILE * sizeof(uint2);
-    const dim3 grid((unsigned)(((size_t)q.width * (size_t)q.local_rows + TILE - 1) / TILE)), block(TILE);
-    AmbientKernelArgs a;
-    for (int k = 0; k < 3; ++k) a.ambient[k] = aa.ambient[k];
-    a.n_rays = aa.n_rays;
-    a.radius = aa.radius;
-    a.variant = aa.variant;
-    // guarded pools and fetch_all select the loop as the reflection pass does
-    if (aa.sky.texels) {
-        if (q.guard)
-            hipLaunchKernelGGL((ambient_list_sky_kernel<MODE, true, false>), grid, block, lds, stream, q, list, cnt, a, aa.sky);
-        else if (q.fetch_all)
-            hipLaunchKernelGGL((ambient_list_sky_kernel<MODE, false, true>), grid, block, lds, stream, q, list, cnt, a, aa.sky);
+    const float sr = ra.specular[0], sg = ra.specular[1], sb = ra.specular[2];
+    return with_loop(p, stack_mode, [&](auto M, auto G, auto FA) {
+        if (ra.sky.texels)
+            hipLaunchKernelGGL((reflect_list_sky_kernel<M(), G(), FA()>), h.grid, dim3(TILE), h.lds, stream, h.q, h.list, h.cnt,
+                               sr, sg, sb, ra.max_bounces, ra.sky);
         else
-            hipLaunchKernelGGL((ambient_list_sky_kernel<MODE, false, false>), grid, block, lds, stream, q, list, cnt, a, aa.sky);
-    }
-    else if (q.guard)
-        hipLaunchKernelGGL((ambient_list_kernel<MODE, true, false>), grid, block, lds, stream, q, list, cnt, a);
-    else if (q.fetch_all)
-        hipLaunchKernelGGL((ambient_list_kernel<MODE, false, true>), grid, block, lds, stream, q, list, cnt, a);
-    else
-        hipLaunchKernelGGL((ambient_list_kernel<MODE, false, false>), grid, block, lds, stream, q, list, cnt, a);
-    return hipGetLastError();
+            hipLaunchKernelGGL((reflect_list_kernel<M(), G(), FA()>), h.grid, dim3(TILE), h.lds, stream, h.q, h.list, h.cnt,
+                               sr, sg, sb, ra.max_bounces);
+    });
 }
 
 hipError_t launch_ambient(const LaunchParams &p, const AmbientArgs &aa, int stack_mode, hipStream_t stream) {
     if (!p.out.hits || !p.out.voxel || !aa.scratch || !svo_ambient::valid_count(aa.n_rays) || aa.variant > 7u ||
         p.width <= 0 || p.local_rows <= 0)
         return hipErrorInvalidValue;
-    // the hit list in the scratch whose head holds the launch's hit masks (rebuilt behind a compacted
-    // shadow pass too: the same masks give the same list)
-    hipError_t e = launch_pack<true>(nullptr, p.width, p.local_rows, aa.scratch, stream);
+    HitList h;   // rebuilt behind a compacted shadow pass too
+    const hipError_t e = pack_hit_list(p, aa.scratch, stream, h);
     if (e != hipSuccess) return e;
-    const int n = ((p.width + 7) / 8) * ((p.local_rows + 7) / 8);
-    const SparseLayout L = sparse_layout(n, p.width * p.local_rows, 4);
-    const uint8_t *base = reinterpret_cast<const uint8_t *>(aa.scratch);
-    const uint32_t *list = reinterpret_cast<const uint32_t *>(base + L.rgb);
-    const uint32_t *cnt = reinterpret_cast<const uint32_t *>(base + L.offsets) + n;
-    LaunchParams q = p;
-    q.out.hitmask = nullptr;
-    return stack_mode == 0 ? launch_ambient_mode<0>(q, list, cnt, aa, stream) : launch_ambient_mode<1>(q, list, cnt, aa, stream);
+    AmbientKernelArgs a;
+    for (int k = 0; k < 3; ++k) a.ambient[k] = aa.ambient[k];
+    a.n_rays = aa.n_rays;
+    a.radius = aa.radius;
+    a.variant = aa.variant;
+    return with_loop(p, stack_mode, [&](auto M, auto G, auto FA) {
+        if (aa.sky.texels)
+            hipLaunchKernelGGL((ambient_list_sky_kernel<M(), G(), FA()>), h.grid, dim3(TILE), h.lds, stream, h.q, h.list, h.cnt, a,
+                               aa.sky);
+        else
+            hipLaunchKernelGGL((ambient_list_kernel<M(), G(), FA()>), h.grid, dim3(TILE), h.lds, stream, h.q, h.list, h.cnt, a);
+    });
 }
 
 hipError_t launch_ambient_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,

@@ -986,39 +986,45 @@ int sample_forms(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p, const Sample
     return SVO_OK;
 }
 
+// The mask scratch: the primary launch writes its tile hit masks to the head of
+// d_shadow_list, sized for the hit list a list pass packs behind them.  Shared between the streams
+// (order_scratch).
+int mask_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
+    const size_t need = svo::shadow_list_bytes(p.width, p.local_rows);
+    if (ctx->shadow_list_cap < need) {
+        HIP_TRY(hipDeviceSynchronize());   // an earlier launch may still read the old list
+        const int rc = regrow(&ctx->d_shadow_list, &ctx->shadow_list_cap, need, need);
+        if (rc) return rc;
+    }
+    const int rc = order_scratch(ctx, L.s);
+    if (rc) return rc;
+    p.out.hitmask = reinterpret_cast<unsigned long long *>(ctx->d_shadow_list);
+    return SVO_OK;
+}
+
 // The two-pass shadow forms' scratch (shared between the streams: order_scratch).
 int shadow_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
-    int rc;
     if ((p.shadows == 1 || p.shadows == 3) && !p.out.hits && !p.out.compact) {   // the second pass reads the records
-        rc = ensure_out(ctx, (size_t)(p.out.frame_layout ? p.height : p.local_rows) * (size_t)p.width);
+        int rc = ensure_out(ctx, (size_t)(p.out.frame_layout ? p.height : p.local_rows) * (size_t)p.width);
         if (rc) return rc;
         rc = order_scratch(ctx, L.s);
         if (rc) return rc;
         p.out.hits = reinterpret_cast<svo::Hit *>(ctx->d_out_hits);
     }
-    if (p.shadows == 3) {   // the compacted pass's masks + hit list (shared scratch, ordered like d_out_hits)
-        const size_t need = svo::shadow_list_bytes(p.width, p.local_rows);
-        if (ctx->shadow_list_cap < need) {
-            HIP_TRY(hipDeviceSynchronize());   // an earlier launch may still read the old list
-            rc = regrow(&ctx->d_shadow_list, &ctx->shadow_list_cap, need, need);
-            if (rc) return rc;
-        }
-        rc = order_scratch(ctx, L.s);
-        if (rc) return rc;
-        p.out.hitmask = reinterpret_cast<unsigned long long *>(ctx->d_shadow_list);
-    }
-    return SVO_OK;
+    // the compacted pass's masks + hit list (ordered like d_out_hits)
+    return p.shadows == 3 ? mask_scratch(ctx, L, p) : SVO_OK;
 }
 
 bool reflection_on(const svo_ctx *ctx) {
     return ctx->max_bounces > 0 && (ctx->specular[0] != 0.0f || ctx->specular[1] != 0.0f || ctx->specular[2] != 0.0f);
 }
 
-// The reflection pass's inputs: per hit pixel the record and the voxel key -- the
-// caller's outputs where it asked for them, else context-owned scratch -- and the hit list's scratch,
-// whose head the primary launch fills with its hit masks (a caller's own masks are copied there behind
-// it: *caller_mask).  Shared between the streams like the shadow forms' scratch (order_scratch).
-int reflect_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p, unsigned long long **caller_mask) {
+// The list passes' inputs (reflection, DESIGN.md 3.2c, and ambient, 3.2e): per hit pixel the record and
+// the voxel key -- the caller's outputs where it asked for them, else context-owned scratch -- and the
+// mask scratch.  *caller_mask: a caller's own masks, which the primary launch fills where they are and
+// the pass copies to the scratch head (copy_caller_mask); null when the masks already lie there (the
+// primary launch writes them there for this pass, or the compacted shadow form already made it).
+int list_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p, unsigned long long **caller_mask) {
     int rc;
     const size_t px = (size_t)(p.out.frame_layout ? p.height : p.local_rows) * (size_t)p.width;
     if (!p.out.hits) {
@@ -1034,24 +1040,27 @@ int reflect_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p, unsigned 
         }
         p.out.voxel = ctx->d_refl_voxel;
     }
-    const size_t need = svo::shadow_list_bytes(p.width, p.local_rows);
-    if (ctx->shadow_list_cap < need) {
-        HIP_TRY(hipDeviceSynchronize());   // an earlier launch may still read the old list
-        rc = regrow(&ctx->d_shadow_list, &ctx->shadow_list_cap, need, need);
-        if (rc) return rc;
-    }
-    rc = order_scratch(ctx, L.s);
+    unsigned long long *given = p.out.hitmask;
+    if (given == reinterpret_cast<unsigned long long *>(ctx->d_shadow_list)) given = nullptr;   // shadow form 2's
+    rc = mask_scratch(ctx, L, p);
     if (rc) return rc;
-    *caller_mask = p.out.hitmask;
-    if (!p.out.hitmask) p.out.hitmask = reinterpret_cast<unsigned long long *>(ctx->d_shadow_list);
+    if (given) p.out.hitmask = given;
+    *caller_mask = given;
+    return SVO_OK;
+}
+
+// A caller's own masks to the scratch head, behind the primary launch that filled them.
+int copy_caller_mask(svo_ctx *ctx, LaunchPlan &L, const unsigned long long *caller_mask) {
+    if (caller_mask)
+        HIP_TRY(hipMemcpyAsync(ctx->d_shadow_list, caller_mask, (size_t)L.n_tiles * sizeof(unsigned long long),
+                               hipMemcpyDeviceToDevice, L.s));
     return SVO_OK;
 }
 
 // Behind the primary launch: compact its hit pixels and follow each one's specular path.
 int reflect_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsigned long long *caller_mask) {
-    if (caller_mask)
-        HIP_TRY(hipMemcpyAsync(ctx->d_shadow_list, caller_mask, (size_t)L.n_tiles * sizeof(unsigned long long),
-                               hipMemcpyDeviceToDevice, L.s));
+    const int rc = copy_caller_mask(ctx, L, caller_mask);
+    if (rc) return rc;
     svo::ReflectArgs ra;
     std::memset(&ra, 0, sizeof ra);
     ra.scratch = ctx->d_shadow_list;
@@ -1067,20 +1076,10 @@ bool ambient_on(const svo_ctx *ctx) {
     return ctx->ambient_rays > 0 && (ctx->ambient[0] != 0.0f || ctx->ambient[1] != 0.0f || ctx->ambient[2] != 0.0f);
 }
 
-// The ambient pass's inputs: the reflection pass's (reflect_scratch).  Behind the
-// compacted shadow form the masks already lie at the head of the shared scratch: they are no caller's.
-int ambient_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p, unsigned long long **caller_mask) {
-    const int rc = reflect_scratch(ctx, L, p, caller_mask);
-    if (rc) return rc;
-    if (*caller_mask == reinterpret_cast<unsigned long long *>(ctx->d_shadow_list)) *caller_mask = nullptr;
-    return SVO_OK;
-}
-
 // Behind the primary launch and its shadow pass: compact the hit pixels and add each one's ambient term.
 int ambient_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsigned long long *caller_mask) {
-    if (caller_mask)
-        HIP_TRY(hipMemcpyAsync(ctx->d_shadow_list, caller_mask, (size_t)L.n_tiles * sizeof(unsigned long long),
-                               hipMemcpyDeviceToDevice, L.s));
+    const int rc = copy_caller_mask(ctx, L, caller_mask);
+    if (rc) return rc;
     svo::AmbientArgs aa;
     std::memset(&aa, 0, sizeof aa);
     aa.scratch = ctx->d_shadow_list;
@@ -1099,17 +1098,7 @@ int ambient_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsign
 // write them to the head of the shared scratch (their list builds leave the head alone).  Otherwise the
 // primary launch writes them there for this pass.
 int sky_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
-    if (p.out.hitmask) return SVO_OK;
-    const size_t need = svo::shadow_list_bytes(p.width, p.local_rows);
-    if (ctx->shadow_list_cap < need) {
-        HIP_TRY(hipDeviceSynchronize());   // an earlier launch may still read the old list
-        const int rc = regrow(&ctx->d_shadow_list, &ctx->shadow_list_cap, need, need);
-        if (rc) return rc;
-    }
-    const int rc = order_scratch(ctx, L.s);
-    if (rc) return rc;
-    p.out.hitmask = reinterpret_cast<unsigned long long *>(ctx->d_shadow_list);
-    return SVO_OK;
+    return p.out.hitmask ? SVO_OK : mask_scratch(ctx, L, p);
 }
 
 // Behind the primary launch (and the reflection pass): every miss pixel's colour from the texture.
@@ -1602,13 +1591,9 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     // only the colours change: a launch that writes none has no reflection pass
     const bool reflect = refl_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
     unsigned long long *caller_mask = nullptr;
-    if (reflect) {
-        rc = reflect_scratch(ctx, L, p, &caller_mask);
-        if (rc) return rc;
-    }
     const bool ambient = amb_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
-    if (ambient) {
-        rc = ambient_scratch(ctx, L, p, &caller_mask);
+    if (reflect || ambient) {   // never both (refused above)
+        rc = list_scratch(ctx, L, p, &caller_mask);
         if (rc) return rc;
     }
     // the same for the sky pass: only a launch that writes a colour has one

@@ -312,6 +312,33 @@ def test_with_a_skybox(torch, oracle_mod, both, masters, bilinear):
         m.SetAmbient(None)
 
 
+# The loops of the pass (stack mode x {guarded, fetch-all, plain}, with and without a skybox) that no test
+# above launches, at tests/test_gpu_reflection.py's small frame and the default setting (4 rays, no radius,
+# variant 0).  The Text fixture's albedo is 0: its cases show that the pass leaves those frames alone.
+LOOP_CASES = [("text", 0, False, 0), ("text", 0, False, 1), ("text", -1, True, 1), ("text", 0, True, 0), ("text", 0, True, 1),
+              ("cyclic7", -1, True, 0), ("cyclic7", -1, True, 1)]
+
+
+@pytest.mark.parametrize("pool,fetch_all,sky,mode", LOOP_CASES)
+def test_render_under_every_loop(torch, oracle_mod, both, pool, fetch_all, sky, mode):
+    from tests.test_gpu_reflection import SMALL, loop_case
+    w, h = SMALL
+    m, svo, cam_name = loop_case(both, pool, fetch_all)
+    try:
+        off = render(torch, m, w, h, mode)
+        hits = int(((off["hits"].view(HIT_DTYPE)["flags"] & 1) != 0).sum())
+        assert hits > 64 and hits % 64 != 0   # more than one wave, the last one partial
+        tex = su.texture(16, 8) if sky else None
+        want = colours(oracle_mod, au.expected_frame(oracle_mod, pool, svo, cam_name, w, h, mode,
+                                                     texture=(tex, True, False) if sky else None))
+        if sky:
+            m.SetSkybox(tex, bilinear=True, clamp_v=False)
+        m.SetAmbient(au.AMBIENT, 4, INF, 0)
+        check_frame(render(torch, m, w, h, mode), want, off, f"{pool} fetch_all {fetch_all} sky {sky} mode {mode}")
+    finally:
+        m.close()
+
+
 # ---------------------------------------------------------------------------- 6. progressive
 def test_progressive_steps_the_variant(torch, oracle_mod, both):
     """Three RenderProgressive samples use variants (v + s) & 7: the accumulation is oracle.accumulate folded

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """The ambient term on the bench's C3 scene (depth-11 Custom1 terrain, 1920x1080): what the ambient
 pass costs a frame, at the flyover and the Main.unity pose, for the settings off, N = 4, 8, 16 at
-radius 8 and N = 4 at radius inf (ambient 0.5, 0.75, 1.0, variant 0).
+radius 8 and N = 4 at radius inf (ambient 0.5, 0.75, 1.0, variant 0) -- and, through the same bracket,
+a reflection frame at the default setting (specular 0.5, 0.25, 0.75, 7 bounces; the term off).
 
 Timing: the whole render of a frame into an RGBA32F device buffer -- the primary launch plus, with
 the term on, the hit list's build and the pass -- bracketed by events on the render's stream.  The
@@ -13,7 +14,8 @@ the same run's off frame.  Not pass/fail numbers.
 Beside the times: the share of open ambient rays per setting, counted on the ray-query API
 (svo_trace_rays -> svo_ambient_rays -> svo_trace_rays), which traces the same rays.
 
-  python tools/ambient_bench.py [--rounds 12] [--block 40] [--bench-json LABEL=FILE ...] [--out profiles/ambient_bench.json]
+  python tools/ambient_bench.py [--rounds 12] [--block 40] [--settings off,N4_r8,reflect] [--bench-json LABEL=FILE ...]
+                               [--out profiles/ambient_bench.json]
 
 --bench-json: result lines of `python bench.py` runs to record beside the figures (the term off,
 this tree and the parent commit's library alternated by the caller), as `label=path` pairs.
@@ -30,7 +32,9 @@ sys.path.insert(0, ROOT)
 
 AMBIENT = (0.5, 0.75, 1.0)
 INF = float("inf")
-SETTINGS = [("off", 0, INF), ("N4_r8", 4, 8.0), ("N8_r8", 8, 8.0), ("N16_r8", 16, 8.0), ("N4_rinf", 4, INF)]
+REFLECT = ((0.5, 0.25, 0.75), 7)
+SETTINGS = [("off", 0, INF), ("N4_r8", 4, 8.0), ("N8_r8", 8, 8.0), ("N16_r8", 16, 8.0), ("N4_rinf", 4, INF),
+            ("reflect", 0, INF)]
 
 
 def open_shares(torch, rm, cam, w, h, mode):
@@ -46,7 +50,7 @@ def open_shares(torch, rm, cam, w, h, mode):
     rm.synchronize()
     primary = int((((d_hits.view(n, 6)[:, 1] >> 16) & 1) != 0).sum())
     out = {}
-    for name, n_rays, radius in SETTINGS[1:]:
+    for name, n_rays, radius in [s for s in SETTINGS if s[1]]:
         d_amb = torch.zeros(n * n_rays * 32, dtype=torch.uint8, device="cuda")
         d_hits2 = torch.zeros(n * n_rays * 6, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()
@@ -75,6 +79,7 @@ def measure(torch, rm, cam, w, h, mode, args):
         order = SETTINGS if r % 2 == 0 else SETTINGS[::-1]
         for name, n_rays, radius in order:
             rm.SetAmbient(AMBIENT if n_rays else None, n_rays or 4, radius, 0)
+            rm.SetReflection(*REFLECT) if name == "reflect" else rm.SetReflection(None)
             evs = []
             with torch.cuda.stream(stream):
                 for _ in range(args.block):
@@ -89,6 +94,7 @@ def measure(torch, rm, cam, w, h, mode, args):
                 times[name].extend(ms.tolist())
                 rounds[name].append(float(np.median(ms)))
     rm.SetAmbient(None)
+    rm.SetReflection(None)
     rm.forget_stream(sptr)
     out = {}
     off = float(np.median(times["off"]))
@@ -107,9 +113,13 @@ def main():
     ap.add_argument("--block", type=int, default=40)
     ap.add_argument("--skip", type=int, default=10)
     ap.add_argument("--max-level", type=int, default=11)
+    ap.add_argument("--settings", default="", help="comma-separated subset of the settings (off is always kept)")
     ap.add_argument("--bench-json", action="append", default=[], metavar="LABEL=FILE")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ambient_bench.json"))
     args = ap.parse_args()
+    if args.settings:
+        keep = set(args.settings.split(",")) | {"off"}
+        SETTINGS[:] = [s for s in SETTINGS if s[0] in keep]
     import torch
     from raytracingtest_amd import RaytracingMaster, build
     from raytracingtest_amd.camera import CAMERAS
