@@ -694,6 +694,73 @@ int svo_ambient_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t fla
 int svo_ambient_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
                           const uint64_t *voxel, int n_rays, float radius, uint32_t variant, svo_ray *rays_out);
 
+/* Lights: up to 8 point lights with shadow rays (opt-in; none by default, and with none every byte and
+ * every launch is what it was).  The reference has _DirectionalLight only (a documented deviation).
+ *
+ * The light rule (csrc/svo_light.h; numpy: lights.py).  Every operation is one IEEE f32 rounding, no fma;
+ * only + - * /, sqrt, compares and selects.  Per traced ray (o, d after the query's clamp), its hit
+ * (t, hit_scale, voxel key, record normal n) and a light (p, R, c, flags):
+ *  1. steps 1-3 of the bounce rule above give the entry axis g, out = d_g > 0 ? -1 : +1 and the origin Q
+ *     (P off the axis g, face_g + out side 2^-6 on it).
+ *  2. L_k = p_k - Q_k.  The light is facing iff L_g out > 0 (ordered; the product is exact): a light behind
+ *     the plane of the face the camera sees lights nothing there.
+ *  3. d2 = (L0 L0 + L1 L1) + L2 L2, u = d2 / (R R).  The light is in range iff u < 1 (ordered; NaN: false).
+ *  4. not facing, or out of range: no ray and no contribution.
+ *  5. the shadow ray is {Q, t_max = 1, dir = L, 0}, traced as svo_trace_rays traces it with flags 0:
+ *     classify, the small-direction clamp (it can move a component of L below 2^-23: the traced direction is
+ *     the clamped one, shading keeps L), the walk, then the t (1 / 64) <= t_max filter on the finished
+ *     record, no early exit.  The direction is the unnormalised L, so parameter 1 is the light itself and a
+ *     hit beyond the light is filtered to a miss.  The pixel is lit by this light iff the record has neither
+ *     flag bit 0 nor bit 4.  A record with only the iteration-cap or stack-overflow flag is lit; a hit at
+ *     t = 0 is occluded.  With SVO_LIGHT_NO_SHADOW the step is skipped: facing and in range means lit.
+ *  6. dist = sqrt(d2); ndl = ((n0 L0 + n1 L1) + n2 L2) / dist; s = ndl > 0 ? ndl : 0, then s < 1 ? s : 1
+ *     (the directional light's saturate; NaN gives 0); w = 1 - u u, then w = w w; a = w / (1 + d2);
+ *     k = s a; contrib_c = (k c_c) alb_c with alb the primary record's DXT albedo.
+ *  7. fold per hit pixel: res = the pixel's colour as rendered with lights off (black if the record carries
+ *     flag bit 3); for j = 0 .. n_lights - 1 in that order, if lit by light j, res_c = res_c + contrib_c;
+ *     alpha 1.
+ * Only rgba, rgba8 and rgb8 change (and through them a progressive accumulation); hits, compact, position,
+ * voxel and hitmask stay the primary ray's, a shadow pass's bit 3 included; miss pixels are untouched.
+ *
+ * svo_set_lights copies the host array.  n_lights outside 0..8; or, in a non-NULL list, a position
+ * component that is not finite or has |p_k| > 2^20, a range not in (0, 2^20], a colour component that is
+ * negative, NaN or > 65536, unknown flag bits: SVO_ERR_ARG, checked before the context is read or a device
+ * touched.  NULL or n_lights 0: off.  Not a svo_config field: svo_config never changes results.  Leaves the
+ * dispatch-order state, tile costs, beam starts, view-change detection and kernel-timing records alone
+ * (SVO_STAGE_KERNEL still brackets the primary kernel only), and the primary launch takes exactly the path
+ * it takes with lights off.  The pass runs behind the primary launch and its shadow pass (all three
+ * shadow_form's), before the sky pass.  Served: svo_render, svo_render_device, svo_render_frame (any band,
+ * layout and stream) and svo_render_progressive(_async); it combines with SVO_OPT_SHADOW_RAYS and a skybox
+ * texture (which only fills miss pixels: lights do not sample it).  svo_count_fetches, svo_beam_starts and
+ * svo_assemble_frame are unaffected; a launch that writes no colour output has no light pass.  Stated
+ * limits, each SVO_ERR_STATE before anything is enqueued: a render with lights and reflection on, with
+ * lights and LOD on, with lights and a non-off ambient setting (the ambient pass rebuilds the direct colour
+ * from the record and would drop the lights' share), svo_render_samples with lights; and a non-empty list
+ * on a multi-device context.  svo_get_lights: copies min(cap, n) lights, *n_lights = n; pointers nullable.
+ *
+ * svo_light_rays: out[i n_lights + j] = the shadow ray of rays[i] toward lights[j] (a HOST array, 1..8
+ * valid lights) if hits[i] has flag bit 0 and the light is facing and in range, else the dead ray
+ * (svo_bounce_rays').  The lights' flags are not read: the call is geometry only.  flags:
+ * SVO_QUERY_RAW_DIRECTIONS only (how rays[i] was traced).  n n_lights <= 2^31 - 1.  Writes nothing past
+ * n n_lights entries; the output must not overlap an input (SVO_ERR_ARG).  NULL pointers, unknown flag
+ * bits, a bad light: SVO_ERR_ARG before any device is touched; n == 0: SVO_OK, nothing launched.  Reads no
+ * pool.  Ray lists 16-byte aligned, records and keys 8-byte.  A multi-device context runs it on
+ * devices[0].  Asynchronous on `stream`; the host form blocks. */
+typedef struct svo_light {      /* 32 bytes */
+    float position[3];          /* world space */
+    float range;                /* world units, finite, 0 < range <= 2^20 */
+    float colour[3];            /* colour x intensity, each finite in [0, 65536] */
+    uint32_t flags;             /* SVO_LIGHT_NO_SHADOW */
+} svo_light;
+enum { SVO_MAX_LIGHTS = 8 };
+enum { SVO_LIGHT_NO_SHADOW = 1 };   /* no shadow ray: facing and in range means lit */
+int svo_set_lights(svo_ctx *ctx, const svo_light *lights, int n_lights);          /* NULL / 0 = off (default) */
+int svo_get_lights(svo_ctx *ctx, svo_light *lights, int cap, int *n_lights);
+int svo_light_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
+                   const uint64_t *d_voxel, const svo_light *lights, int n_lights, svo_ray *d_rays_out, void *stream);
+int svo_light_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
+                        const uint64_t *voxel, const svo_light *lights, int n_lights, svo_ray *rays_out);
+
 /* Information about the uploaded pool. */
 int svo_get_info(svo_ctx *ctx, size_t *n_nodes, int *max_depth, int *device);
 

@@ -39,7 +39,8 @@ EXPORTS = ("svo_create", "svo_set_buffer", "svo_set_buffer_v2", "svo_set_camera"
            "svo_set_config", "svo_beam_starts", "svo_trace_rays", "svo_trace_rays_host", "svo_set_lod", "svo_get_lod",
            "svo_trace_rays_lod", "svo_trace_rays_lod_host", "svo_bounce_rays", "svo_bounce_rays_host",
            "svo_set_reflection", "svo_get_reflection", "svo_set_skybox", "svo_get_skybox", "svo_sample_sky",
-           "svo_sample_sky_host", "svo_set_ambient", "svo_get_ambient", "svo_ambient_rays", "svo_ambient_rays_host")
+           "svo_sample_sky_host", "svo_set_ambient", "svo_get_ambient", "svo_ambient_rays", "svo_ambient_rays_host",
+           "svo_set_lights", "svo_get_lights", "svo_light_rays", "svo_light_rays_host")
 # svo_ray: one caller-supplied ray of svo_trace_rays (world space, direction used as given)
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")])
 assert RAY_DTYPE.itemsize == 32
@@ -48,6 +49,11 @@ HIT_INVALID_RAY = 0x10                       # svo_hit.flags bit 4: the query's 
 SKY_BILINEAR, SKY_CLAMP_V = 1, 2             # svo_set_skybox flags
 SKY_MAX_DIM = 8192                           # largest skybox width / height
 AMBIENT_MAX_RAYS = 16                        # svo_set_ambient: n_rays is 4, 8 or 16
+# svo_light: one point light of svo_set_lights / svo_light_rays
+LIGHT_DTYPE = np.dtype([("position", "<f4", (3,)), ("range", "<f4"), ("colour", "<f4", (3,)), ("flags", "<u4")])
+assert LIGHT_DTYPE.itemsize == 32
+LIGHT_NO_SHADOW = 1                          # svo_light.flags: no shadow ray
+MAX_LIGHTS = 8                               # svo_set_lights: at most 8 lights
 SVO_OPT_SHADOW_RAYS = 1
 SVO_OPT_KERNEL_TIMING = 2
 SVO_OPT_COUNT_BEAM = 4
@@ -209,6 +215,10 @@ def lib():
         "svo_get_ambient": [vp, ctypes.POINTER(f), ctypes.POINTER(i), ctypes.POINTER(f), ctypes.POINTER(ctypes.c_uint32)],
         "svo_ambient_rays": [vp, vp, sz, ctypes.c_uint32, vp, vp, i, f, ctypes.c_uint32, vp, vp],
         "svo_ambient_rays_host": [vp, vp, sz, ctypes.c_uint32, vp, vp, i, f, ctypes.c_uint32, vp],
+        "svo_set_lights": [vp, vp, i],
+        "svo_get_lights": [vp, vp, i, ctypes.POINTER(i)],
+        "svo_light_rays": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, i, vp, vp],
+        "svo_light_rays_host": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, i, vp],
         "svo_destroy": [vp],
         "svo_last_error": [],
         "svo_abi_version": [],

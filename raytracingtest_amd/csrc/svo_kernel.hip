@@ -14,6 +14,7 @@
 #include "svo_traverse.h"
 #include "svo_reflect.h"
 #include "svo_ambient.h"
+#include "svo_light.h"
 
 #include <hipcub/hipcub.hpp>   // ordered ray queries: the toolchain's device radix sort (launch_query_sort)
 
@@ -2003,6 +2004,103 @@ __global__ __launch_bounds__(TILE) void ambient_list_sky_kernel(LaunchParams p, 
                                              a.variant, tex);
 }
 
+// ------------------------------------------------------------ light pass
+// svo_light_rays: entry e = i * n_lights + j of the output is the shadow ray of rays[i] toward light j
+// (svo_light.h light_entry).  One thread per entry, two 16-byte stores; the output is n_lights times the
+// input and must not overlap it (checked by the host).  Reads no pool.
+struct LightKernelArgs {   // one kernel argument beside LaunchParams (which does not grow)
+    svo_lights::Light l[svo_lights::MAX_LIGHTS];
+    int n;
+};
+
+__global__ __launch_bounds__(256) void light_rays_kernel(const QueryRay *__restrict__ rays, uint32_t n, uint32_t flags,
+                                                         const Hit *__restrict__ hits,
+                                                         const unsigned long long *__restrict__ voxel, LightKernelArgs a,
+                                                         QueryRay *__restrict__ out) {
+    const size_t e = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (e >= (size_t)n * (size_t)a.n) return;
+    const uint32_t i = (uint32_t)(e / (uint32_t)a.n);
+    const int j = (int)(e - (size_t)i * (uint32_t)a.n);
+    const uint4 *src = reinterpret_cast<const uint4 *>(rays) + 2 * (size_t)i;
+    const uint4 ra = src[0], rb = src[1];
+    const uint2 *rec = reinterpret_cast<const uint2 *>(hits + i);
+    const uint2 h0 = rec[0], h1 = rec[1], h2 = rec[2];
+    const uint32_t ray[8] = { ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w };
+    const uint32_t hit[6] = { h0.x, h0.y, h1.x, h1.y, h2.x, h2.y };
+    // the light by selects over the eight kernel-argument entries: j differs between lanes
+    svo_lights::Light l = a.l[0];
+#pragma unroll
+    for (int q = 1; q < svo_lights::MAX_LIGHTS; ++q)
+        if (j == q) l = a.l[q];
+    uint32_t o[8];
+    svo_lights::light_entry(ray, hit, voxel[i], (flags & QUERY_RAW) != 0, l, o, nullptr);
+    uint4 *dst = reinterpret_cast<uint4 *>(out) + 2 * e;
+    dst[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// svo_set_lights: point lights with shadow rays, in the list-pass frame.  A lane starts
+// from its pixel's camera ray and primary record (out.hits, out.voxel): res = the primary colour, and the
+// entry face of the voxel (svo_reflect.h entry_face, once per lane) gives the common origin Q of its
+// shadow rays.  The light loop is outermost and wave-uniform: light j comes out of the kernel argument
+// through scalar loads, and every lane computes L = p - Q, facing and in range (svo_light.h light_vector).
+// A lane whose light is facing and in range traces {Q, 1, L, 0} as a query does with flags 0: classify
+// (such a ray is always valid), the clamp (shading keeps the unclamped L), the primary rays' loop, then the
+// t (1 / 64) <= 1 filter on the finished record -- no early exit; the direction is the unnormalised L, so
+// a hit beyond the light is a miss.  trace_lean runs under `if (go)` only when the wave's ballot of `go` is
+// non-zero: a wave wholly behind or out of range of a light does no walk for it, and SVO_LIGHT_NO_SHADOW
+// (wave-uniform) skips the walk altogether.  A lit lane adds (k c) albedo to res, in j order, in registers,
+// with no cross-lane sum.  Hit pixels' colours are overwritten with plain stores; records, keys, positions
+// and masks stay the primary ray's.
+template <int MODE, bool GUARD, bool FA>
+__global__ __launch_bounds__(TILE) void light_list_kernel(LaunchParams p, const uint32_t *__restrict__ list,
+                                                          const uint32_t *__restrict__ count, LightKernelArgs a) {
+    extern __shared__ uint2 stk_base[];
+    ListEntry le;
+    if (!list_entry(p, list, count, le)) return;
+    const bool mine = le.mine;
+    float org[3] = {0.0f, 0.0f, 0.0f}, res[3] = {0.0f, 0.0f, 0.0f}, alb[3] = {0.0f, 0.0f, 0.0f};
+    float nrm[3] = {0.0f, 0.0f, 0.0f}, out = 1.0f;
+    int g = 0;
+    if (mine) {
+        float t, o[3], d[3];
+        int scale;
+        primary_colour(p, le.i, t, nrm, scale, alb, res);
+        camera_ray(p.cam, p.width, p.height, le.x, le.gy, o, d);
+        g = svo_reflect::entry_face(o, d, t, scale, p.out.voxel[le.i], org, &out);
+    }
+    uint2 *stk = stk_base + threadIdx.x;
+#pragma nounroll
+    for (int j = 0; j < a.n; ++j) {
+        const svo_lights::Light &l = a.l[j];   // uniform j: scalar loads
+        float L[3], d2, u;
+        bool facing, in_range;
+        svo_lights::light_vector(org, g, out, l.position, l.range, L, &d2, &u, &facing, &in_range);
+        const bool go = mine && facing && in_range;
+        bool lit = go;
+        if (!(l.flags & svo_lights::NO_SHADOW) && LM_OF(go) != 0) {   // wave-uniform
+            if (go) {
+                float dir[3] = {L[0], L[1], L[2]};
+                svo_reflect::clamp_direction(dir, false);
+                Ray r;
+                setup_ray(org, dir, r);
+                FRay f;
+                to_fray(r, f);
+                trace_lean<MODE, GUARD, false, FA>(p, f, stk);
+                from_fray(f, r);
+                bool hit = r.scale < S_MAX;
+                if (hit) {
+                    const float t_min = r.t_min * 32.0f;
+                    hit = (t_min * 64.0f) * (1.0f / 64.0f) <= 1.0f;
+                }
+                lit = !hit;
+            }
+        }
+        if (lit) svo_lights::add_light(res, svo_lights::light_factor(nrm, L, d2, u), l.colour, alb);
+    }
+    if (mine) store_colour(p.out, le.i, res);
+}
+
 // ------------------------------------------------------------------ skybox
 // svo_set_skybox: the sky pass behind the primary launch.  One wave64 per 8x8 tile of the
 // launch's rows, in plain tile order (the pass has no heavy tiles to put first).  The tile's hit mask is
@@ -3167,6 +3265,39 @@ hipError_t launch_ambient_rays(const QueryRay *rays, uint32_t n, uint32_t flags,
     const size_t total = (size_t)n * (size_t)n_rays;
     hipLaunchKernelGGL(ambient_rays_kernel, dim3((unsigned)((total + 255u) / 256u)), dim3(256), 0, stream, rays, n, flags, hits,
                        voxel, n_rays, radius, variant, out);
+    return hipGetLastError();
+}
+
+static bool light_kernel_args(const svo_lights::Light *lights, int n_lights, LightKernelArgs &a) {
+    if (!lights || n_lights < 1 || n_lights > svo_lights::MAX_LIGHTS) return false;
+    std::memset(&a, 0, sizeof a);
+    for (int j = 0; j < n_lights; ++j) a.l[j] = lights[j];
+    a.n = n_lights;
+    return true;
+}
+
+hipError_t launch_lights(const LaunchParams &p, const LightArgs &la, int stack_mode, hipStream_t stream) {
+    LightKernelArgs a;
+    if (!p.out.hits || !p.out.voxel || !la.scratch || !light_kernel_args(la.lights, la.n_lights, a) || p.width <= 0 ||
+        p.local_rows <= 0)
+        return hipErrorInvalidValue;
+    HitList h;   // rebuilt behind a compacted shadow pass too
+    const hipError_t e = pack_hit_list(p, la.scratch, stream, h);
+    if (e != hipSuccess) return e;
+    return with_loop(p, stack_mode, [&](auto M, auto G, auto FA) {
+        hipLaunchKernelGGL((light_list_kernel<M(), G(), FA()>), h.grid, dim3(TILE), h.lds, stream, h.q, h.list, h.cnt, a);
+    });
+}
+
+hipError_t launch_light_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
+                             const unsigned long long *voxel, const svo_lights::Light *lights, int n_lights, QueryRay *out,
+                             hipStream_t stream) {
+    LightKernelArgs a;
+    if (!rays || !hits || !voxel || !out || !light_kernel_args(lights, n_lights, a)) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    const size_t total = (size_t)n * (size_t)n_lights;
+    hipLaunchKernelGGL(light_rays_kernel, dim3((unsigned)((total + 255u) / 256u)), dim3(256), 0, stream, rays, n, flags, hits,
+                       voxel, a, out);
     return hipGetLastError();
 }
 

@@ -42,6 +42,7 @@
 
 #include "svo_rt.h"
 #include "svo_ambient.h"
+#include "svo_light.h"
 #include "svo_beam.h"
 #include "svo_lod.h"
 #include "svo_sched.h"
@@ -282,6 +283,10 @@ struct svo_ctx {
     int ambient_rays = 0;
     float ambient_radius = std::numeric_limits<float>::infinity();
     uint32_t ambient_variant = 0, ambient_step = 0;
+    // point lights of the renders (svo_set_lights; none: off -- DESIGN.md 3.2g): the pass shares the
+    // reflection pass's scratch (the two never run together); the list travels as a kernel argument
+    svo_lights::Light lights[svo_lights::MAX_LIGHTS] = {};
+    int n_lights = 0;
     // diagnostics (the library's only environment switches, read once at svo_create):
     // SVO_DEBUG bit 0 the loop-form / class-table decision trace, bit 1 the order each launch
     // takes; SVO_WAVE_LOG=<file> the per-wave record; SVO_BEAM_DIAG the splat's timing variants
@@ -1093,6 +1098,19 @@ int ambient_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsign
     return SVO_OK;
 }
 
+// Behind the primary launch and its shadow pass: compact the hit pixels and add each one's point lights.
+int light_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsigned long long *caller_mask) {
+    const int rc = copy_caller_mask(ctx, L, caller_mask);
+    if (rc) return rc;
+    svo::LightArgs la;
+    la.scratch = ctx->d_shadow_list;
+    la.lights = ctx->lights;
+    la.n_lights = ctx->n_lights;
+    const hipError_t e = svo::launch_lights(p, la, L.stack_mode, L.s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("light launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
 // The sky pass's input: the launch's tile hit masks.  A caller's own masks are read
 // where they are; so are shadow form 2's and the reflection pass's, which already made the primary launch
 // write them to the head of the shared scratch (their list builds leave the head alone).  Otherwise the
@@ -1562,6 +1580,12 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     if (amb_on && sa) return fail(SVO_ERR_STATE, "svo_render_samples with an ambient term is not supported");
     if (amb_on && refl_on) return fail(SVO_ERR_STATE, "an ambient term with reflection is not supported");
     if (amb_on && lod) return fail(SVO_ERR_STATE, "an ambient term with LOD is not supported");
+    // point lights (svo_set_lights): a pass behind the primary rays and their shadow pass
+    const bool lights_on = ctx->n_lights > 0 && !out.fetches && !out.starts;
+    if (lights_on && sa) return fail(SVO_ERR_STATE, "svo_render_samples with lights is not supported");
+    if (lights_on && refl_on) return fail(SVO_ERR_STATE, "lights with reflection are not supported");
+    if (lights_on && lod) return fail(SVO_ERR_STATE, "lights with LOD are not supported");
+    if (lights_on && amb_on) return fail(SVO_ERR_STATE, "lights with an ambient term are not supported");
     // skybox (svo_set_skybox): a pass behind the primary rays (and the bounces) that recolours the misses;
     // svo_render_samples blends in its own launch's epilogue, before any pass could run
     const bool sky_on = ctx->sky.texels && !out.fetches && !out.starts;
@@ -1592,7 +1616,8 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     const bool reflect = refl_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
     unsigned long long *caller_mask = nullptr;
     const bool ambient = amb_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
-    if (reflect || ambient) {   // never both (refused above)
+    const bool lights = lights_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
+    if (reflect || ambient || lights) {   // never two of them (refused above)
         rc = list_scratch(ctx, L, p, &caller_mask);
         if (rc) return rc;
     }
@@ -1634,6 +1659,10 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     }
     if (ambient) {
         rc = ambient_pass(ctx, L, p, caller_mask);
+        if (rc) return rc;
+    }
+    if (lights) {
+        rc = light_pass(ctx, L, p, caller_mask);
         if (rc) return rc;
     }
     if (sky) {
@@ -2223,6 +2252,51 @@ int ambient_device(const void *d_rays, size_t n, uint32_t flags, const void *d_h
     return SVO_OK;
 }
 
+// A light list as svo_set_lights and svo_light_rays take it (host memory): n_lights in 0 .. 8, and with a
+// non-NULL list every light valid (svo_light.h light_error).
+int check_light_list(const svo_light *lights, int n_lights) {
+    static_assert(sizeof(svo_light) == sizeof(svo_lights::Light), "svo_light layout");
+    if (n_lights < 0 || n_lights > svo_lights::MAX_LIGHTS) return fail(SVO_ERR_ARG, "n_lights must lie in 0..8");
+    for (int j = 0; lights && j < n_lights; ++j) {
+        svo_lights::Light l;
+        std::memcpy(&l, lights + j, sizeof l);
+        if (const char *msg = svo_lights::light_error(l)) return fail(SVO_ERR_ARG, "light " + std::to_string(j) + ": " + msg);
+    }
+    return SVO_OK;
+}
+
+// The argument checks of svo_light_rays(_host) that need no device.
+int check_light_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const void *hits, const void *voxel,
+                     const svo_light *lights, int n_lights, const void *rays_out) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!rays) return fail(SVO_ERR_ARG, "null ray list");
+    if (!hits) return fail(SVO_ERR_ARG, "null hit records");
+    if (!voxel) return fail(SVO_ERR_ARG, "null voxel keys");
+    if (!rays_out) return fail(SVO_ERR_ARG, "null output ray list");
+    if (flags & ~(uint32_t)SVO_QUERY_RAW_DIRECTIONS) return fail(SVO_ERR_ARG, "unknown light-ray flag bits");
+    if (!lights) return fail(SVO_ERR_ARG, "null light list");
+    if (n_lights < 1) return fail(SVO_ERR_ARG, "n_lights must lie in 1..8");
+    if (int rc = check_light_list(lights, n_lights)) return rc;
+    if (n > MAX_QUERY_RAYS / (size_t)n_lights) return fail(SVO_ERR_ARG, "more than 2^31 - 1 light rays in one batch");
+    const size_t out_bytes = 32 * n * (size_t)n_lights;
+    if (ranges_overlap(rays_out, out_bytes, rays, 32 * n) || ranges_overlap(rays_out, out_bytes, hits, 24 * n) ||
+        ranges_overlap(rays_out, out_bytes, voxel, 8 * n))
+        return fail(SVO_ERR_ARG, "the output ray list overlaps an input");
+    return SVO_OK;
+}
+
+int light_device(const void *d_rays, size_t n, uint32_t flags, const void *d_hits, const void *d_voxel,
+                 const svo_light *lights, int n_lights, void *d_rays_out, hipStream_t s) {
+    const hipError_t e = svo::launch_light_rays(reinterpret_cast<const svo::QueryRay *>(d_rays), (uint32_t)n,
+                                                (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u,
+                                                reinterpret_cast<const svo::Hit *>(d_hits),
+                                                reinterpret_cast<const unsigned long long *>(d_voxel),
+                                                reinterpret_cast<const svo_lights::Light *>(lights), n_lights,
+                                                reinterpret_cast<svo::QueryRay *>(d_rays_out), s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("light ray launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
 int check_sky_args(svo_ctx *ctx, const float *dirs, size_t n, const float *rgba) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
     if (!dirs) return fail(SVO_ERR_ARG, "null direction list");
@@ -2414,6 +2488,55 @@ int svo_ambient_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t 
         return SVO_OK;
     } catch (const std::exception &e) {
         return fail(SVO_ERR_HIP, std::string("svo_ambient_rays_host: ") + e.what());
+    }
+}
+
+int svo_light_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
+                   const uint64_t *d_voxel, const svo_light *lights, int n_lights, svo_ray *d_rays_out, void *stream) {
+    int rc = check_light_args(ctx, d_rays, n, flags, d_hits, d_voxel, lights, n_lights, d_rays_out);
+    if (rc) return rc;
+    if (((uintptr_t)d_rays | (uintptr_t)d_rays_out) & 15u) return fail(SVO_ERR_ARG, "ray lists must be 16-byte aligned");
+    if (((uintptr_t)d_hits | (uintptr_t)d_voxel) & 7u) return fail(SVO_ERR_ARG, "hit records and voxel keys must be 8-byte aligned");
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        return light_device(d_rays, n, flags, d_hits, d_voxel, lights, n_lights, d_rays_out,
+                            stream ? (hipStream_t)stream : c->stream);
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_light_rays: ") + e.what());
+    }
+}
+
+int svo_light_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
+                        const uint64_t *voxel, const svo_light *lights, int n_lights, svo_ray *rays_out) {
+    int rc = check_light_args(ctx, rays, n, flags, hits, voxel, lights, n_lights, rays_out);
+    if (rc) return rc;
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        // staged layout: rays (32 B), hit records (24 B), voxel keys (8 B) per input, then the output rays
+        const size_t off_hits = 32 * n, off_vox = 56 * n, off_out = 64 * n, out_bytes = 32 * n * (size_t)n_lights;
+        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, off_out + out_bytes);
+        if (rc) return rc;
+        rc = order_query_scratch(c, c->stream);
+        if (rc) return rc;
+        char *base = static_cast<char *>(c->q_host);
+        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
+            hipStream_t s;
+            ~Drain() { hipStreamSynchronize(s); }
+        } drain{c->stream};
+        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(base + off_hits, hits, 24 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(base + off_vox, voxel, 8 * n, hipMemcpyHostToDevice, c->stream));
+        rc = light_device(base, n, flags, base + off_hits, base + off_vox, lights, n_lights, base + off_out, c->stream);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(rays_out, base + off_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SVO_OK;
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_light_rays_host: ") + e.what());
     }
 }
 
@@ -2766,6 +2889,27 @@ int svo_get_ambient(svo_ctx *ctx, float ambient[3], int *n_rays, float *radius, 
     if (n_rays) *n_rays = ctx->ambient_rays;
     if (radius) *radius = ctx->ambient_radius;
     if (variant) *variant = ctx->ambient_variant;
+    return SVO_OK;
+}
+
+int svo_set_lights(svo_ctx *ctx, const svo_light *lights, int n_lights) {
+    if (int rc = check_light_list(lights, n_lights)) return rc;   // before the context is read
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    const int n = lights ? n_lights : 0;
+    if (n > 0 && is_multi(ctx)) return fail(SVO_ERR_STATE, "lights on a multi-device context are not supported");
+    for (int j = 0; j < svo_lights::MAX_LIGHTS; ++j) {
+        svo_lights::Light l{};
+        if (j < n) std::memcpy(&l, lights + j, sizeof l);
+        ctx->lights[j] = l;
+    }
+    ctx->n_lights = n;
+    return SVO_OK;
+}
+
+int svo_get_lights(svo_ctx *ctx, svo_light *lights, int cap, int *n_lights) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    for (int j = 0; lights && j < cap && j < ctx->n_lights; ++j) std::memcpy(lights + j, ctx->lights + j, sizeof(svo_light));
+    if (n_lights) *n_lights = ctx->n_lights;
     return SVO_OK;
 }
 

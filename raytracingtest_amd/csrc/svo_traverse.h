@@ -13,6 +13,7 @@
 
 #include <algorithm>
 
+#include "svo_light.h"
 #include "svo_sky.h"
 
 namespace svo {
@@ -289,6 +290,18 @@ struct AmbientArgs {
 };
 hipError_t launch_ambient(const LaunchParams &p, const AmbientArgs &aa, int stack_mode, hipStream_t stream);
 
+// Light pass (svo_set_lights; svo_kernel.hip light_list_kernel, svo_light.h is the rule), behind a render
+// launch's primary rays and its shadow pass: the hit list as the reflection pass builds it, one wave64 per 64
+// entries, at most one shadow ray per entry and light.  p: the launch's own parameters; out.hits and out.voxel
+// hold the primary records (with the shadow pass's bit 3) and keys, the colour outputs among out.rgba /
+// rgba8 / rgb8 are overwritten for the hit pixels.
+struct LightArgs {
+    void *scratch;                      // shadow_list_bytes, its head the launch's hit masks
+    const svo_lights::Light *lights;     // host
+    int n_lights;                       // 1 .. 8
+};
+hipError_t launch_lights(const LaunchParams &p, const LightArgs &la, int stack_mode, hipStream_t stream);
+
 // Skybox (svo_set_skybox; svo_sky.h is the rule).
 // Sky pass behind a render launch's primary rays (sky_fill_kernel): one wave64 per 8x8 tile of the launch's
 // rows reads the tile's hit mask (masks: svo_frame.hitmask's layout, band-local tiles) as one wave-uniform
@@ -343,5 +356,12 @@ hipError_t launch_bounce_rays(const QueryRay *rays, uint32_t n, uint32_t flags, 
 hipError_t launch_ambient_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
                                const unsigned long long *voxel, int n_rays, float radius, uint32_t variant, QueryRay *out,
                                hipStream_t stream);
+
+// svo_light_rays: out[i * n_lights + j] = the shadow ray (svo_light.h) of rays[i] and hits[i] / voxel[i]
+// toward lights[j] (host), or the dead ray.  flags: QUERY_RAW.  A flat launch, one thread per output entry;
+// out must not overlap the inputs.
+hipError_t launch_light_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
+                             const unsigned long long *voxel, const svo_lights::Light *lights, int n_lights, QueryRay *out,
+                             hipStream_t stream);
 
 }  // namespace svo

@@ -207,6 +207,26 @@ class RaytracingMaster:
         check(_lib.lib().svo_get_ambient(self._ctx, a, ctypes.byref(n), ctypes.byref(r), ctypes.byref(v)), "svo_get_ambient")
         return (a[0], a[1], a[2]), n.value, r.value, v.value
 
+    def SetLights(self, lights):
+        """Point lights with shadow rays (svo_set_lights; lights.py is the rule): up to 8 lights, each
+        (position, range, colour[, flags]) or a LIGHT_DTYPE record; None or an empty list: off, the default.
+        A hit pixel whose entry face looks toward a light within its range, with nothing between the two
+        (LIGHT_NO_SHADOW: unchecked), gets the light's colour times the albedo, the cosine and a smooth
+        falloff that reaches 0 at `range`.  Only the colour outputs change."""
+        from .lights import make_lights
+        before = self.GetLights().tobytes()
+        rec = make_lights(lights if lights is not None else [])
+        check(_lib.lib().svo_set_lights(self._ctx, rec.ctypes.data if len(rec) else None, len(rec)), "svo_set_lights")
+        if self.GetLights().tobytes() != before:   # another image: the accumulation restarts
+            self.currentSample = 0
+
+    def GetLights(self):
+        """The context's lights (svo_get_lights): LIGHT_DTYPE [n]."""
+        n = ctypes.c_int()
+        out = np.zeros(_lib.MAX_LIGHTS, _lib.LIGHT_DTYPE)
+        check(_lib.lib().svo_get_lights(self._ctx, out.ctypes.data, _lib.MAX_LIGHTS, ctypes.byref(n)), "svo_get_lights")
+        return out[:n.value].copy()
+
     def SetSkybox(self, texels, bilinear=True, clamp_v=False):
         """~ RayTracingShader.SetTexture(0, "_SkyboxTexture", SkyboxTexture) (RaytracingMaster.cs:28;
         svo_set_skybox): an equirectangular panorama for the rays that leave the scene.  texels: H x W x 4
@@ -548,6 +568,34 @@ class RaytracingMaster:
         results of the batch's trace."""
         check(_lib.lib().svo_ambient_rays(self._ctx, rays_ptr, int(n), self._query_flags(False, raw), hits, voxel,
                                           int(n_rays), float(radius), int(variant), out, stream), "svo_ambient_rays")
+
+    def LightRays(self, rays, hits, voxel, lights, raw=False):
+        """The shadow rays of a traced batch toward each light (svo_light_rays_host; lights.light_rays is its
+        numpy statement): rays, their hit records and voxel keys as TraceRays returned them; raw: whether the
+        batch was traced with raw=True.  Returns RAY_DTYPE [n * n_lights], entry i * n_lights + j = the ray of
+        rays[i] toward lights[j] with t_max 1 (the light itself): a dead ray where there was no hit, or the
+        light lies behind the entry face or out of range."""
+        from .lights import make_lights
+        rays = np.ascontiguousarray(rays, _lib.RAY_DTYPE).reshape(-1)
+        hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+        voxel = np.ascontiguousarray(voxel, np.uint64).reshape(-1)
+        if not len(rays) == len(hits) == len(voxel):
+            raise ValueError(f"{len(rays)} rays, {len(hits)} hit records, {len(voxel)} voxel keys")
+        rec = make_lights(lights)
+        out = np.zeros(len(rays) * len(rec), _lib.RAY_DTYPE)
+        check(_lib.lib().svo_light_rays_host(self._ctx, rays.ctypes.data, len(rays), self._query_flags(False, raw),
+                                             hits.ctypes.data, voxel.ctypes.data, rec.ctypes.data, len(rec),
+                                             out.ctypes.data), "svo_light_rays_host")
+        return out
+
+    def light_rays_device(self, rays_ptr, n, hits, voxel, out, lights, raw=False, stream=None):
+        """Asynchronous svo_light_rays on device buffers: rays_ptr = n svo_ray records, out = n * n_lights
+        (16-byte aligned, no overlap with the inputs), hits (n x 24 bytes) and voxel (n uint64) the results
+        of the batch's trace; lights: host records (the call copies them before it returns)."""
+        from .lights import make_lights
+        rec = make_lights(lights)
+        check(_lib.lib().svo_light_rays(self._ctx, rays_ptr, int(n), self._query_flags(False, raw), hits, voxel,
+                                        rec.ctypes.data, len(rec), out, stream), "svo_light_rays")
 
     def beam_starts_device(self, width, height, starts_ptr, band=None, stream=None):
         """svo_beam_starts: every primary ray's beam start (SVO-space t, -inf: the cube entry) into a

@@ -110,6 +110,24 @@ public static class SvoNative {
     [DllImport(Lib)] public static extern int svo_ambient_rays_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr n, uint flags,
                                                                     [In] SvoHit[] hits, [In] ulong[] voxel, int nRays,
                                                                     float radius, uint variant, [Out] SvoRay[] raysOut);
+    // Lights (svo_rt.h): up to 8 point lights with shadow rays -- the renders' setting and the ray queries' building block
+    public const int MaxLights = 8;
+    public const uint LightNoShadow = 1;
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoLight {          // svo_light, 32 bytes
+        public Vector3 position;      // world space, |component| <= 2^20
+        public float range;           // world units, in (0, 2^20]
+        public Vector3 colour;        // colour x intensity, each in [0, 65536]
+        public uint flags;            // LightNoShadow
+    }
+    [DllImport(Lib)] public static extern int svo_set_lights(IntPtr ctx, [In] SvoLight[] lights, int nLights);
+    [DllImport(Lib)] public static extern int svo_get_lights(IntPtr ctx, [Out] SvoLight[] lights, int cap, out int nLights);
+    [DllImport(Lib)] public static extern int svo_light_rays(IntPtr ctx, IntPtr dRays, UIntPtr n, uint flags, IntPtr dHits,
+                                                             IntPtr dVoxel, [In] SvoLight[] lights, int nLights,
+                                                             IntPtr dRaysOut, IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_light_rays_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr n, uint flags,
+                                                                  [In] SvoHit[] hits, [In] ulong[] voxel,
+                                                                  [In] SvoLight[] lights, int nLights, [Out] SvoRay[] raysOut);
     // Skybox (svo_rt.h): the reference's _SkyboxTexture for rays that leave the scene, and its rule for ray queries
     public const uint SkyBilinear = 1, SkyClampV = 2;
     [DllImport(Lib)] public static extern int svo_set_skybox(IntPtr ctx, [In] Color[] rgba, int width, int height, uint flags);
@@ -393,6 +411,24 @@ public class RaytracingMasterNative : MonoBehaviour {
         }
         Graphics.Blit(_frame, destination);   // already accumulated: a plain copy, no AddMaterial
         _currentSample++;
+    }
+
+    // Point lights of the scene on the voxel world (svo_set_lights; it changes the image; the reference has
+    // _DirectionalLight only): up to 8 Unity point lights, colour x intensity, Light.range as the range.  Call it
+    // when the lights change; null or an empty array turns them off.  Not supported together with specular,
+    // lodPixels, ambient or gpus > 1.
+    public void SetLights(Light[] pointLights, bool shadows = true) {
+        int n = pointLights == null ? 0 : Mathf.Min(pointLights.Length, SvoNative.MaxLights);
+        var rec = new SvoNative.SvoLight[n];
+        for (int j = 0; j < n; ++j) {
+            Color c = pointLights[j].color * pointLights[j].intensity;
+            rec[j].position = pointLights[j].transform.position;
+            rec[j].range = pointLights[j].range;
+            rec[j].colour = new Vector3(c.r, c.g, c.b);
+            rec[j].flags = shadows && pointLights[j].shadows != LightShadows.None ? 0u : SvoNative.LightNoShadow;
+        }
+        SvoNative.Check(SvoNative.svo_set_lights(_ctx, n > 0 ? rec : null, n), "svo_set_lights");
+        _currentSample = 0;   // another image: a fresh accumulation
     }
 
     void OnDestroy() {
