@@ -761,6 +761,101 @@ int svo_light_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags
 int svo_light_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
                         const uint64_t *voxel, const svo_light *lights, int n_lights, svo_ray *rays_out);
 
+/* Scene objects: sub-SVOs of the context's pool placed in the world (opt-in; none by default, and with
+ * none every byte and every launch is what it was).  An object is a tree uploaded behind the terrain with
+ * svo_set_buffer(.., dst_offset) -- v1 descriptors are relative, so it is uploaded as it is -- and a
+ * placement: a position, a rotation and a power-of-two scale.  Moving it is one svo_set_objects call; no
+ * pool is rebuilt.  The reference only sketched this (Clipmap.compute's chunk loop, never compiled in).
+ *
+ * The object rule (csrc/svo_object.h; numpy: objects.py).  Every operation is one IEEE f32 rounding, no
+ * fma; only + - * /, compares and selects.  A world ray (o, d, t_max) and an object (root, k, p, R), with
+ * s = 2^-k (exact):
+ *  1. classify the world ray as svo_trace_rays does: a non-finite component, a NaN t_max or an all-zero d
+ *     makes it invalid, and an invalid ray has no candidate anywhere.
+ *  2. q_i = o_i - p_i; o'_j = ((R_0j q_0 + R_1j q_1) + R_2j q_2) s; d'_j = ((R_0j d_0 + R_1j d_1) + R_2j d_2) s.
+ *     Origin and direction take the same exact scale, so the ray parameter is shared: a record's t / 64 is
+ *     the world ray's own parameter for the terrain and for every object.
+ *  3. the object ray is {o', t_max, d', 0}.  It is classified again (d' can underflow to zero, o' can
+ *     overflow): invalid means no candidate in this object.  Unless SVO_QUERY_RAW_DIRECTIONS is set, the
+ *     small-direction clamp applies to d'.  Note: (x 1 + y 0) + z 0 turns a -0 component into +0, so an
+ *     identity placement is byte-identical to svo_trace_rays only for rays without negative-zero components.
+ *  4. cube test (part of the rule: the walk's t_min is not provably monotone in f32).  t_in, t_out = the
+ *     walk's own entry (after its max(.., 0)) and exit of the cube [1, 2]^3 for the clamped object ray;
+ *     t_entry = fl(fl(32 t_in) 64).  The object is walked iff t_in <= t_out (ordered) and (the best record so
+ *     far is a miss or t_entry < best.t).  Otherwise no walk and no candidate.
+ *  5. the walk is IntersectSVO exactly as the query runs it, in the given stack mode, with parent = root
+ *     after the ray setup; then the query's t (1 / 64) <= t_max filter on the finished record.  The record's
+ *     parent is the absolute pool index; hit_idx, hit_scale, t and the flags are the walk's own; the normal
+ *     is rotated to world, n_i = (R_i0 m_0 + R_i1 m_1) + R_i2 m_2 with m the walk's record normal, not
+ *     renormalised.  Position and voxel key stay OBJECT-LOCAL (the hit position's definition on the object
+ *     ray); the world hit point is o + (t / 64) d.
+ *  6. fold.  Candidates in a fixed order: the terrain (root 0, the world ray traced as svo_trace_rays traces
+ *     it) unless SVO_SCENE_NO_TERRAIN, then objects 0 .. n - 1.  The best is the first candidate with flag
+ *     bit 0; a later one replaces it iff its t < the best t (ordered, strict: ties keep the earlier).  If
+ *     nothing hit, the result is the terrain's record when the terrain was a candidate (its iteration-cap
+ *     and overflow flags survive, and an invalid ray keeps its flag 0x10), else the plain miss record.
+ *     Object id: -1 a miss, 0 the terrain, j + 1 object j.
+ * Every walk of a scene query and of the object pass runs the guarded loop form on the 21-slot stack (proven
+ * safe on cyclic and over-deep pools; the same bytes as the unguarded form on proper trees), so nothing
+ * about an object's subtree needs validating.  A ray that leaves an object's root pops parent 0.
+ *
+ * svo_object_rays: out[i] = the object ray of steps 2-3 BEFORE the clamp, {o', t_max, d', 0}; the dead ray
+ * of svo_bounce_rays when the world ray is invalid.  Geometry only: reads no pool, the object's root is
+ * not read.  d_rays_out may be d_rays.  flags: SVO_QUERY_RAW_DIRECTIONS is accepted and changes nothing (the
+ * result is the unclamped ray either way); any other bit, a NULL pointer, an invalid object, n > 2^31 - 1:
+ * SVO_ERR_ARG before any device is touched; n == 0: SVO_OK, nothing launched.  Ray lists 16-byte aligned.
+ * Asynchronous on `stream`; the host form blocks.  A multi-device context runs it on devices[0].
+ *
+ * svo_trace_scene: svo_trace_rays over the terrain and `objects`, a HOST array of 0 .. 8 objects (copied
+ * before the call returns).  The context's own list is neither read nor changed.  flags:
+ * SVO_QUERY_RAW_DIRECTIONS and SVO_SCENE_NO_TERRAIN; SVO_QUERY_ORDERED is SVO_ERR_ARG in this version.
+ * Outputs as svo_trace_rays' (every non-NULL output fully written, mask tail bits 0) plus d_object (nullable,
+ * n entries); out and d_object not all NULL.  n_objects == 0 without SVO_SCENE_NO_TERRAIN gives
+ * svo_trace_rays' bytes.  An invalid object, n_objects outside 0 .. 8, a root >= the context's capacity:
+ * SVO_ERR_ARG before any device is touched.  A root past the uploaded nodes reads the zero descriptor and
+ * hits nothing.  No pool uploaded: SVO_ERR_STATE.  The host form has no mask output.
+ *
+ * svo_set_objects: the list used by renders; the host array is copied, NULL or 0 turns objects off.  Not
+ * a svo_config field.  It leaves the dispatch-order state, tile costs, beam starts, view-change detection
+ * and kernel-timing records alone, and the primary launch takes exactly the path it takes without objects.
+ * The object pass runs behind the primary launch and before the sky pass: per pixel the camera ray (traced
+ * as given, like the primary ray: no clamp, t_max +inf), the primary record as the best so far, steps 2-6
+ * for objects 0 .. n - 1.  A pixel whose best changed gets every output the launch writes: hits (rotated
+ * normal) and compact; position and voxel, object-local; colour through the Shade rule with the rotated
+ * normal and the new record's DXT albedo in rgba, rgba8 and rgb8 (and through them a progressive
+ * accumulation); its bit in the tile's hit-mask word, so a skybox leaves it alone.  Untouched pixels keep
+ * every byte.  Which object a pixel shows is readable from `parent` (objects live in their own pool ranges).
+ * Served: svo_render, svo_render_device, svo_render_frame (any band, layout and stream) and
+ * svo_render_progressive(_async); it combines with a skybox texture.  svo_count_fetches, svo_beam_starts and
+ * svo_assemble_frame are unaffected; a compact part rebuilds an object pixel's normal from `parent`
+ * UNROTATED, so a one-process-per-GPU split with objects sends dense RGB parts.  Stated limits, each
+ * SVO_ERR_STATE before anything is enqueued: a render with a non-empty list and SVO_OPT_SHADOW_RAYS,
+ * reflection, an ambient term, lights or LOD, svo_render_samples with objects; and a non-empty list on a
+ * multi-device context (refused by svo_set_objects).  svo_get_objects: copies min(cap, n) objects,
+ * *n_objects = n; pointers nullable. */
+typedef struct svo_object {     /* 64 bytes */
+    uint32_t root;              /* descriptor index of the object's root in the context's pool */
+    int32_t  scale_log2;        /* k in [-8, 8]: the object's cube has side 32 * 2^k world units */
+    uint32_t flags;             /* 0 (no bits defined yet; unknown bits: SVO_ERR_ARG) */
+    float    position[3];       /* world position of the cube's centre, finite, |p| <= 2^20 */
+    float    rotation[9];       /* row-major R, world = R * object; every entry of R R^T - I within
+                                   2^-10 (checked in float64), det > 0 */
+    uint32_t reserved;          /* 0 */
+} svo_object;
+enum { SVO_MAX_OBJECTS = 8 };
+enum { SVO_SCENE_NO_TERRAIN = 4 };   /* svo_trace_scene flags: the terrain (root 0) is no candidate */
+int svo_set_objects(svo_ctx *ctx, const svo_object *objects, int n_objects);        /* NULL / 0 = off (default) */
+int svo_get_objects(svo_ctx *ctx, svo_object *objects, int cap, int *n_objects);
+int svo_object_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_object *object,
+                    svo_ray *d_rays_out, void *stream);
+int svo_object_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_object *object,
+                         svo_ray *rays_out);
+int svo_trace_scene(svo_ctx *ctx, const svo_ray *d_rays, size_t n, int stack_mode, uint32_t flags,
+                    const svo_object *objects, int n_objects, const svo_query_out *out, int32_t *d_object, void *stream);
+int svo_trace_scene_host(svo_ctx *ctx, const svo_ray *rays, size_t n, int stack_mode, uint32_t flags,
+                         const svo_object *objects, int n_objects, svo_hit *hits, float *position, uint64_t *voxel,
+                         int32_t *object);
+
 /* Information about the uploaded pool. */
 int svo_get_info(svo_ctx *ctx, size_t *n_nodes, int *max_depth, int *device);
 

@@ -40,7 +40,9 @@ EXPORTS = ("svo_create", "svo_set_buffer", "svo_set_buffer_v2", "svo_set_camera"
            "svo_trace_rays_lod", "svo_trace_rays_lod_host", "svo_bounce_rays", "svo_bounce_rays_host",
            "svo_set_reflection", "svo_get_reflection", "svo_set_skybox", "svo_get_skybox", "svo_sample_sky",
            "svo_sample_sky_host", "svo_set_ambient", "svo_get_ambient", "svo_ambient_rays", "svo_ambient_rays_host",
-           "svo_set_lights", "svo_get_lights", "svo_light_rays", "svo_light_rays_host")
+           "svo_set_lights", "svo_get_lights", "svo_light_rays", "svo_light_rays_host",
+           "svo_set_objects", "svo_get_objects", "svo_object_rays", "svo_object_rays_host", "svo_trace_scene",
+           "svo_trace_scene_host")
 # svo_ray: one caller-supplied ray of svo_trace_rays (world space, direction used as given)
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")])
 assert RAY_DTYPE.itemsize == 32
@@ -54,6 +56,12 @@ LIGHT_DTYPE = np.dtype([("position", "<f4", (3,)), ("range", "<f4"), ("colour", 
 assert LIGHT_DTYPE.itemsize == 32
 LIGHT_NO_SHADOW = 1                          # svo_light.flags: no shadow ray
 MAX_LIGHTS = 8                               # svo_set_lights: at most 8 lights
+# svo_object: one placed sub-SVO of svo_set_objects / svo_trace_scene / svo_object_rays
+OBJECT_DTYPE = np.dtype([("root", "<u4"), ("scale_log2", "<i4"), ("flags", "<u4"), ("position", "<f4", (3,)),
+                         ("rotation", "<f4", (9,)), ("reserved", "<u4")])
+assert OBJECT_DTYPE.itemsize == 64
+MAX_OBJECTS = 8                              # svo_set_objects / svo_trace_scene: at most 8 objects
+SCENE_NO_TERRAIN = 4                         # svo_trace_scene flags: the terrain (root 0) is no candidate
 SVO_OPT_SHADOW_RAYS = 1
 SVO_OPT_KERNEL_TIMING = 2
 SVO_OPT_COUNT_BEAM = 4
@@ -219,6 +227,12 @@ def lib():
         "svo_get_lights": [vp, vp, i, ctypes.POINTER(i)],
         "svo_light_rays": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, i, vp, vp],
         "svo_light_rays_host": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, i, vp],
+        "svo_set_objects": [vp, vp, i],
+        "svo_get_objects": [vp, vp, i, ctypes.POINTER(i)],
+        "svo_object_rays": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp],
+        "svo_object_rays_host": [vp, vp, sz, ctypes.c_uint32, vp, vp],
+        "svo_trace_scene": [vp, vp, sz, i, ctypes.c_uint32, vp, i, ctypes.POINTER(SvoQueryOut), vp, vp],
+        "svo_trace_scene_host": [vp, vp, sz, i, ctypes.c_uint32, vp, i, vp, vp, vp, vp],
         "svo_destroy": [vp],
         "svo_last_error": [],
         "svo_abi_version": [],

@@ -15,6 +15,7 @@
 #include "svo_reflect.h"
 #include "svo_ambient.h"
 #include "svo_light.h"
+#include "svo_object.h"
 
 #include <hipcub/hipcub.hpp>   // ordered ray queries: the toolchain's device radix sort (launch_query_sort)
 
@@ -259,13 +260,15 @@ struct LeanDiag {            // DIAG instantiation only (env SVO_WAVE_LOG)
 // becomes `leaf | small` below -- one multiply, one add and one compare per trip on values already live.
 template <int MODE, bool GUARD, bool DIAG = false, bool FETCH_ALL = false, bool COUNT = false, bool LOD = false>
 __device__ __forceinline__ void trace_lean(const LaunchParams &p, FRay &r, uint2 *__restrict__ stk,
-                                           LeanDiag *diag = nullptr) {
+                                           LeanDiag *diag = nullptr, int own_slots = 0) {
     // GUARD = false (host-proven, svo_rt.hip launch / recompute_depth): one tree of
     // known depth, fewer than 2^29 nodes, and (HLSL stack) parent indices below
     // 2^24, so a PUSH never overflows the stack, the HLSL round trip of a parent
     // index is the identity and node byte offsets fit 32 bits.
     constexpr int STRIDE = TILE;
-    const int slots = p.slots;
+    // own_slots (a compile-time constant at every call site): an object walk's own 21-slot stack, whatever
+    // the pool's proven depth (svo_object.h; r.parent is then the object's root, set by the caller)
+    const int slots = own_slots ? own_slots : p.slots;
     // a ray that leaves the root pops the top slot (the root's entry: parent 0) -- every lane,
     // finished ones too, fetches nodes[parent] on every trip (!GUARD), so it must hold a node
     for (int s = 0; s < slots; ++s) stk[s * STRIDE] = make_uint2(0u, 0u);
@@ -2101,6 +2104,221 @@ __global__ __launch_bounds__(TILE) void light_list_kernel(LaunchParams p, const 
     if (mine) store_colour(p.out, le.i, res);
 }
 
+// ----------------------------------------------------------- scene objects
+// svo_set_objects / svo_trace_scene (svo_object.h is the rule): sub-SVOs of the pool placed
+// in the world.  The object table is one kernel argument, read through scalar loads (every loop over it is
+// wave-uniform).
+struct ObjectKernelArgs {   // one kernel argument beside LaunchParams (which does not grow)
+    svo_objects::Object o[svo_objects::MAX_OBJECTS];
+    int n;
+};
+constexpr int OBJECT_SLOTS = 21;   // the guarded loop's full stack (scales 2 .. 22), whatever the pool's depth
+
+// svo_object_rays: out[i] = rays[i] in the object's frame (svo_object.h object_entry).  One thread per ray;
+// a thread reads its own ray before it writes its own slot, so out may be rays (no __restrict__ on either).
+// Reads no pool.
+__global__ __launch_bounds__(256) void object_rays_kernel(const QueryRay *rays, uint32_t n, svo_objects::Object ob,
+                                                          QueryRay *out) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const uint4 *src = reinterpret_cast<const uint4 *>(rays) + 2 * (size_t)i;
+    const uint4 a = src[0], b = src[1];
+    const uint32_t ray[8] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w };
+    uint32_t o[8];
+    svo_objects::object_entry(ray, ob, o);
+    uint4 *dst = reinterpret_cast<uint4 *>(out) + 2 * (size_t)i;
+    dst[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
+// Steps 2-4 of the rule for one lane and one object (wave-uniform `ob`): the clamped object ray (o2, d2),
+// its setup and whether the lane walks the object.  live: the lane has a valid world ray (o, d).
+__device__ __forceinline__ bool object_setup(const svo_objects::Object &ob, bool live, const float o[3], const float d[3],
+                                             bool raw, bool best_hit, float best_t, float o2[3], float d2[3], Ray &r) {
+    svo_objects::object_ray(o, d, ob, o2, d2);
+    const bool ok = live && svo_objects::valid_ray(o2, d2, 0.0f);   // t_max was classified with the world ray
+    svo_reflect::clamp_direction(d2, raw);
+    setup_ray(o2, d2, r);   // r.t_min / r.t_max: the cube's entry (after max(.., 0)) and exit
+    return ok && svo_objects::cube_test(r.t_min, r.t_max, best_hit, best_t);
+}
+
+// Step 5 for the lanes with `go` (the caller's branch is wave-uniform: the ballot of go is non-zero): the
+// guarded walk from `root` on its own 21-slot stack, then the finished record of a candidate.  R: the
+// object's rotation for the normal (rotate false: the terrain, whose normal stays as decoded).  shade: Result colour
+// through shade_hit with that normal and the record's DXT albedo.  want_pos: position and voxel key from the
+// traced ray's own origin and direction (object-local for an object).  Returns flag bit 0 after the t_max
+// filter; a candidate that did not hit holds the miss record with the walk's cap / overflow flags (the
+// plain one when the filter removed a hit), as svo_trace_rays returns it.
+template <int MODE>
+__device__ __forceinline__ bool candidate_walk(const LaunchParams &p, Ray &r, uint32_t root, bool rotate, const float R[9],
+                                               const float o2[3], const float d2[3], float t_lim, bool shade,
+                                               bool want_pos, uint2 *__restrict__ stk, Record &c) {
+    FRay f;
+    to_fray(r, f);
+    f.parent = root;
+    trace_lean<MODE, true>(p, f, stk, nullptr, OBJECT_SLOTS);
+    from_fray(f, r);
+    miss_record(c, r.flags & 0xFFFFu);
+    if (r.scale >= S_MAX) return false;
+    const float t = (r.t_min * 32.0f) * 64.0f;            // N:163, N:171
+    if (!(t * (1.0f / 64.0f) <= t_lim)) {
+        miss_record(c, 0u);
+        return false;
+    }
+    const int hit_idx = r.idx ^ r.octant_mask ^ 7;        // N:176
+    // a guarded walk's parent can lie past the pool only on a miss (it then read the zero descriptor)
+    const uint2 a = p.att[r.parent];                      // N:177-178
+    float m[3], n[3];
+    decode_normal(a.y >> 16, m);
+    normalize3(m);
+    svo_objects::world_normal(R, m, n);
+    if (!rotate) { n[0] = m[0]; n[1] = m[1]; n[2] = m[2]; }
+    c.w[0] = r.parent;
+    c.w[1] = (uint32_t)hit_idx | ((uint32_t)r.scale << 8) | (((r.flags | 1u) & 0xFFFFu) << 16);
+    c.w[2] = __float_as_uint(t);
+    c.w[3] = __float_as_uint(n[0]); c.w[4] = __float_as_uint(n[1]); c.w[5] = __float_as_uint(n[2]);
+    if (shade) {
+        float alb[3];
+        decode_dxt(a.x, a.y, hit_idx, alb);
+        shade_hit(p.cam, n, alb, c.rgb);
+    }
+    if (want_pos) hit_position(r, o2, d2, c);
+    return true;
+}
+
+// svo_trace_scene: one wave64 per 64 consecutive rays; the outer loop over the candidates -- the terrain
+// (c = 0, root 0, the world ray as svo_trace_rays traces it: no cube test), then object c - 1 -- is
+// wave-uniform and no lane leaves before the stores.  A candidate is walked under `if (go)` only when the
+// wave's ballot of go is non-zero (trace_lean's lane masks come from exec and must not be empty): a wave
+// whose rays all fail an object's cube test does no walk for it.  Every walk, the terrain's too, runs the
+// guarded loop on the 21-slot stack: the same bytes as the unguarded form on a proper tree, and safe on
+// whatever a later upload makes of an object's subtree.  first: 0, or 1 with SVO_SCENE_NO_TERRAIN.
+template <int MODE>
+__global__ __launch_bounds__(TILE) void scene_rays_kernel(LaunchParams p, QueryArgs q, ObjectKernelArgs a, int first,
+                                                          int32_t *__restrict__ object_id) {
+    extern __shared__ uint2 stk_base[];
+    const int lane = (int)threadIdx.x;
+    const uint32_t i = blockIdx.x * TILE + (uint32_t)lane;
+    const bool in = i < q.n;
+    const bool raw = (q.flags & QUERY_RAW) != 0;
+    float o[3] = {0.0f, 0.0f, 0.0f}, d[3] = {0.0f, 0.0f, 0.0f}, t_lim = 0.0f;
+    if (in) {
+        const float4 *src = reinterpret_cast<const float4 *>(q.rays) + 2 * (size_t)i;
+        const float4 ra = src[0], rb = src[1];
+        o[0] = ra.x; o[1] = ra.y; o[2] = ra.z; t_lim = ra.w;
+        d[0] = rb.x; d[1] = rb.y; d[2] = rb.z;
+    }
+    const bool live = in && svo_objects::valid_ray(o, d, t_lim);
+    const bool want_pos = q.out.position || q.out.voxel;
+    Record best;
+    miss_record(best, (first == 0 && !live) ? HIT_INVALID_RAY : 0u);   // svo_trace_rays' record of an invalid ray
+    bool best_hit = false;
+    int32_t id = -1;
+    uint2 *stk = stk_base + lane;
+#pragma nounroll
+    for (int c = first; c <= a.n; ++c) {
+        const svo_objects::Object &ob = a.o[c > 0 ? c - 1 : 0];   // uniform c: scalar loads
+        float o2[3], d2[3];
+        Ray r;
+        bool go;
+        if (c == 0) {
+            o2[0] = o[0]; o2[1] = o[1]; o2[2] = o[2];
+            d2[0] = d[0]; d2[1] = d[1]; d2[2] = d[2];
+            svo_reflect::clamp_direction(d2, raw);
+            setup_ray(o2, d2, r);
+            go = live;
+        } else {
+            go = object_setup(ob, live, o, d, raw, best_hit, __uint_as_float(best.w[2]), o2, d2, r);
+        }
+        if (LM_OF(go) == 0) continue;   // wave-uniform
+        if (go) {
+            Record cand;
+            const bool hit = candidate_walk<MODE>(p, r, c == 0 ? 0u : ob.root, c != 0, ob.rotation, o2, d2, t_lim, false,
+                                                  want_pos, stk, cand);
+            if (c == 0) best = cand;   // the terrain's record stands until something hits nearer, a miss too
+            if (hit && svo_objects::replaces(best_hit, __uint_as_float(best.w[2]), __uint_as_float(cand.w[2]))) {
+                best = cand;
+                best_hit = true;
+                id = c;
+            }
+        }
+    }
+    if (in) {
+        store_outputs(q.out, i, best);
+        if (object_id) object_id[i] = id;
+    }
+    if (q.out.hitmask) {
+        const lmask m = LM_OF(best_hit);   // lanes past the list: bit 0
+        if (lane == 0) q.out.hitmask[blockIdx.x] = m;
+    }
+}
+
+// The object pass of a render (svo_set_objects), behind the primary launch and before the sky pass: one
+// wave64 per 8x8 tile of the launch's rows in plain tile order.  A lane rebuilds its camera ray, takes the
+// primary record's t and hit bit (out.hits or out.compact) as the best so far and runs steps 2-6 of the
+// rule over the objects; a pixel whose best changed gets every output of the launch rewritten at the
+// render's own addresses, and its bit or-ed into the tile's hit-mask word (masks: the caller's or the sky
+// pass's scratch, nullable), so a sky pass behind this one leaves it alone.  Untouched pixels keep every byte.
+template <int MODE>
+__global__ __launch_bounds__(TILE) void object_pass_kernel(LaunchParams p, ObjectKernelArgs a,
+                                                           unsigned long long *__restrict__ masks, int tiles_x) {
+    extern __shared__ uint2 stk_base[];
+    const int lane = (int)threadIdx.x;
+    const int t = (int)blockIdx.x;
+    const int bx = t % tiles_x, by = t / tiles_x;
+    const int x = bx * 8 + (lane & 7);
+    const int lr = by * 8 + (lane >> 3);
+    const bool inside = x < p.width && lr < p.local_rows;
+    const int gy = global_row(p, inside ? lr : 0);
+    const size_t i = out_index(p, inside ? lr : 0, gy, inside ? x : 0);
+    float o[3], d[3];
+    camera_ray(p.cam, p.width, p.height, x, gy, o, d);
+    const float t_lim = __builtin_inff();   // a primary ray has no t_max
+    const bool live = inside && svo_objects::valid_ray(o, d, t_lim);
+    bool best_hit = false;
+    float best_t = 0.0f;
+    if (inside) {
+        uint32_t w1, w2;
+        if (p.out.hits) {
+            const uint2 *rec = reinterpret_cast<const uint2 *>(p.out.hits + i);
+            w1 = rec[0].y; w2 = rec[1].x;
+        } else {
+            w1 = p.out.compact[3 * i + 1]; w2 = p.out.compact[3 * i + 2];
+        }
+        best_hit = ((w1 >> 16) & 1u) != 0u;
+        best_t = __uint_as_float(w2);
+    }
+    const bool shade = p.out.rgba || p.out.rgba8 || p.out.rgb8;
+    const bool want_pos = p.out.position || p.out.voxel;
+    Record best;
+    miss_record(best, 0u);
+    bool changed = false;
+    uint2 *stk = stk_base + lane;
+#pragma nounroll
+    for (int j = 0; j < a.n; ++j) {
+        const svo_objects::Object &ob = a.o[j];   // uniform j: scalar loads
+        float o2[3], d2[3];
+        Ray r;
+        const bool go = object_setup(ob, live, o, d, true, best_hit, best_t, o2, d2, r);
+        if (LM_OF(go) == 0) continue;   // wave-uniform
+        if (go) {
+            Record cand;
+            const bool hit = candidate_walk<MODE>(p, r, ob.root, true, ob.rotation, o2, d2, t_lim, shade, want_pos, stk, cand);
+            if (hit && svo_objects::replaces(best_hit, best_t, __uint_as_float(cand.w[2]))) {
+                best = cand;
+                best_hit = true;
+                best_t = __uint_as_float(cand.w[2]);
+                changed = true;
+            }
+        }
+    }
+    if (changed) store_outputs(p.out, i, best);
+    if (masks) {
+        const lmask m = LM_OF(changed);
+        if (m != 0 && lane == 0) masks[t] |= m;
+    }
+}
+
 // ------------------------------------------------------------------ skybox
 // svo_set_skybox: the sky pass behind the primary launch.  One wave64 per 8x8 tile of the
 // launch's rows, in plain tile order (the pass has no heavy tiles to put first).  The tile's hit mask is
@@ -3298,6 +3516,49 @@ hipError_t launch_light_rays(const QueryRay *rays, uint32_t n, uint32_t flags, c
     const size_t total = (size_t)n * (size_t)n_lights;
     hipLaunchKernelGGL(light_rays_kernel, dim3((unsigned)((total + 255u) / 256u)), dim3(256), 0, stream, rays, n, flags, hits,
                        voxel, a, out);
+    return hipGetLastError();
+}
+
+static bool object_kernel_args(const svo_objects::Object *objects, int n_objects, ObjectKernelArgs &a) {
+    if (n_objects < 0 || n_objects > svo_objects::MAX_OBJECTS || (n_objects > 0 && !objects)) return false;
+    std::memset(&a, 0, sizeof a);
+    for (int j = 0; j < n_objects; ++j) a.o[j] = objects[j];
+    a.n = n_objects;
+    return true;
+}
+
+hipError_t launch_object_rays(const QueryRay *rays, uint32_t n, const svo_objects::Object &object, QueryRay *out,
+                              hipStream_t stream) {
+    if (!rays || !out) return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(object_rays_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, rays, n, object, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_scene_query(const LaunchParams &p, const QueryArgs &q, const svo_objects::Object *objects, int n_objects,
+                              bool terrain, int32_t *object_id, int stack_mode, hipStream_t stream) {
+    ObjectKernelArgs a;
+    if (!object_kernel_args(objects, n_objects, a) || q.index) return hipErrorInvalidValue;
+    if (q.n == 0) return hipSuccess;
+    const size_t lds = (size_t)OBJECT_SLOTS * TILE * sizeof(uint2) + lds_pad();
+    const dim3 grid((q.n + (uint32_t)TILE - 1u) / (uint32_t)TILE), block(TILE);
+    const int first = terrain ? 0 : 1;
+    if (stack_mode == 0) hipLaunchKernelGGL((scene_rays_kernel<0>), grid, block, lds, stream, p, q, a, first, object_id);
+    else hipLaunchKernelGGL((scene_rays_kernel<1>), grid, block, lds, stream, p, q, a, first, object_id);
+    return hipGetLastError();
+}
+
+hipError_t launch_objects(const LaunchParams &p, const svo_objects::Object *objects, int n_objects, int stack_mode,
+                          hipStream_t stream) {
+    ObjectKernelArgs a;
+    if (!object_kernel_args(objects, n_objects, a) || n_objects < 1 || (!p.out.hits && !p.out.compact) || p.width <= 0 ||
+        p.local_rows <= 0)
+        return hipErrorInvalidValue;
+    const int bx = (p.width + 7) / 8, by = (p.local_rows + 7) / 8;
+    const size_t lds = (size_t)OBJECT_SLOTS * TILE * sizeof(uint2) + lds_pad();
+    const dim3 grid((unsigned)(bx * by)), block(TILE);
+    if (stack_mode == 0) hipLaunchKernelGGL((object_pass_kernel<0>), grid, block, lds, stream, p, a, p.out.hitmask, bx);
+    else hipLaunchKernelGGL((object_pass_kernel<1>), grid, block, lds, stream, p, a, p.out.hitmask, bx);
     return hipGetLastError();
 }
 

@@ -43,6 +43,7 @@
 #include "svo_rt.h"
 #include "svo_ambient.h"
 #include "svo_light.h"
+#include "svo_object.h"
 #include "svo_beam.h"
 #include "svo_lod.h"
 #include "svo_sched.h"
@@ -287,6 +288,10 @@ struct svo_ctx {
     // reflection pass's scratch (the two never run together); the list travels as a kernel argument
     svo_lights::Light lights[svo_lights::MAX_LIGHTS] = {};
     int n_lights = 0;
+    // placed sub-SVOs of the renders (svo_set_objects; none: off -- DESIGN.md 3.2h): the list travels as a
+    // kernel argument of the object pass
+    svo_objects::Object objects[svo_objects::MAX_OBJECTS] = {};
+    int n_objects = 0;
     // diagnostics (the library's only environment switches, read once at svo_create):
     // SVO_DEBUG bit 0 the loop-form / class-table decision trace, bit 1 the order each launch
     // takes; SVO_WAVE_LOG=<file> the per-wave record; SVO_BEAM_DIAG the splat's timing variants
@@ -1111,6 +1116,25 @@ int light_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsigned
     return SVO_OK;
 }
 
+// The object pass's input: the primary records.  A caller's hits or compact records are
+// read (and rewritten) where they are; a launch that asked for neither writes them to context scratch.
+int object_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
+    if (p.out.hits || p.out.compact) return SVO_OK;
+    int rc = ensure_out(ctx, (size_t)(p.out.frame_layout ? p.height : p.local_rows) * (size_t)p.width);
+    if (rc) return rc;
+    rc = order_scratch(ctx, L.s);
+    if (rc) return rc;
+    p.out.hits = reinterpret_cast<svo::Hit *>(ctx->d_out_hits);
+    return SVO_OK;
+}
+
+// Behind the primary launch, before the sky pass: every pixel where a placed object is nearer.
+int object_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p) {
+    const hipError_t e = svo::launch_objects(p, ctx->objects, ctx->n_objects, L.stack_mode, L.s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("object launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
 // The sky pass's input: the launch's tile hit masks.  A caller's own masks are read
 // where they are; so are shadow form 2's and the reflection pass's, which already made the primary launch
 // write them to the head of the shared scratch (their list builds leave the head alone).  Otherwise the
@@ -1586,6 +1610,16 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     if (lights_on && refl_on) return fail(SVO_ERR_STATE, "lights with reflection are not supported");
     if (lights_on && lod) return fail(SVO_ERR_STATE, "lights with LOD are not supported");
     if (lights_on && amb_on) return fail(SVO_ERR_STATE, "lights with an ambient term are not supported");
+    // placed objects (svo_set_objects): a pass behind the primary rays that takes every pixel where an object
+    // is nearer; the other passes do not know the objects yet
+    const bool objects_on = ctx->n_objects > 0 && !out.fetches && !out.starts;
+    if (objects_on && sa) return fail(SVO_ERR_STATE, "svo_render_samples with objects is not supported");
+    if (objects_on && (ctx->options & SVO_OPT_SHADOW_RAYS))
+        return fail(SVO_ERR_STATE, "objects with shadow rays are not supported");
+    if (objects_on && refl_on) return fail(SVO_ERR_STATE, "objects with reflection are not supported");
+    if (objects_on && amb_on) return fail(SVO_ERR_STATE, "objects with an ambient term are not supported");
+    if (objects_on && lights_on) return fail(SVO_ERR_STATE, "objects with lights are not supported");
+    if (objects_on && lod) return fail(SVO_ERR_STATE, "objects with LOD are not supported");
     // skybox (svo_set_skybox): a pass behind the primary rays (and the bounces) that recolours the misses;
     // svo_render_samples blends in its own launch's epilogue, before any pass could run
     const bool sky_on = ctx->sky.texels && !out.fetches && !out.starts;
@@ -1619,6 +1653,10 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     const bool lights = lights_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
     if (reflect || ambient || lights) {   // never two of them (refused above)
         rc = list_scratch(ctx, L, p, &caller_mask);
+        if (rc) return rc;
+    }
+    if (objects_on) {   // the records change too: every launch has the pass
+        rc = object_scratch(ctx, L, p);
         if (rc) return rc;
     }
     // the same for the sky pass: only a launch that writes a colour has one
@@ -1663,6 +1701,10 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     }
     if (lights) {
         rc = light_pass(ctx, L, p, caller_mask);
+        if (rc) return rc;
+    }
+    if (objects_on) {
+        rc = object_pass(ctx, L, p);
         if (rc) return rc;
     }
     if (sky) {
@@ -2297,6 +2339,90 @@ int light_device(const void *d_rays, size_t n, uint32_t flags, const void *d_hit
     return SVO_OK;
 }
 
+// An object list as svo_set_objects and svo_trace_scene take it (host memory): n_objects in 0 .. 8, and with
+// a non-NULL list every object valid (svo_object.h object_error).  The roots' bound needs the context:
+// check_object_roots.
+int check_object_list(const svo_object *objects, int n_objects) {
+    static_assert(sizeof(svo_object) == sizeof(svo_objects::Object), "svo_object layout");
+    if (n_objects < 0 || n_objects > svo_objects::MAX_OBJECTS) return fail(SVO_ERR_ARG, "n_objects must lie in 0..8");
+    for (int j = 0; objects && j < n_objects; ++j) {
+        svo_objects::Object ob;
+        std::memcpy(&ob, objects + j, sizeof ob);
+        if (const char *msg = svo_objects::object_error(ob)) return fail(SVO_ERR_ARG, "object " + std::to_string(j) + ": " + msg);
+    }
+    return SVO_OK;
+}
+
+int check_object_roots(const svo_ctx *c, const svo_object *objects, int n_objects) {
+    for (int j = 0; objects && j < n_objects; ++j)
+        if ((size_t)objects[j].root >= c->capacity)
+            return fail(SVO_ERR_ARG, "object " + std::to_string(j) + ": root outside the node-pool capacity");
+    return SVO_OK;
+}
+
+// The argument checks of svo_object_rays(_host) that need no device.
+int check_object_ray_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const svo_object *object,
+                          const void *rays_out) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!rays) return fail(SVO_ERR_ARG, "null ray list");
+    if (!rays_out) return fail(SVO_ERR_ARG, "null output ray list");
+    if (!object) return fail(SVO_ERR_ARG, "null object");
+    if (flags & ~(uint32_t)SVO_QUERY_RAW_DIRECTIONS) return fail(SVO_ERR_ARG, "unknown object-ray flag bits");
+    if (int rc = check_object_list(object, 1)) return rc;
+    if (n > MAX_QUERY_RAYS) return fail(SVO_ERR_ARG, "more than 2^31 - 1 rays in one batch");
+    return SVO_OK;
+}
+
+int object_rays_device(const void *d_rays, size_t n, const svo_object *object, void *d_rays_out, hipStream_t s) {
+    svo_objects::Object ob;
+    std::memcpy(&ob, object, sizeof ob);
+    const hipError_t e = svo::launch_object_rays(reinterpret_cast<const svo::QueryRay *>(d_rays), (uint32_t)n, ob,
+                                                 reinterpret_cast<svo::QueryRay *>(d_rays_out), s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("object ray launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
+// The argument checks of svo_trace_scene(_host) that need no device: `any_out` = some output was asked for.
+int check_scene_args(svo_ctx *ctx, const void *rays, size_t n, int stack_mode, uint32_t flags, const svo_object *objects,
+                     int n_objects, bool any_out) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!rays) return fail(SVO_ERR_ARG, "null ray list");
+    if (!any_out) return fail(SVO_ERR_ARG, "every scene-query output is null");
+    if (flags & SVO_QUERY_ORDERED) return fail(SVO_ERR_ARG, "SVO_QUERY_ORDERED is not supported by scene queries");
+    if (flags & ~(uint32_t)(SVO_QUERY_RAW_DIRECTIONS | SVO_SCENE_NO_TERRAIN)) return fail(SVO_ERR_ARG, "unknown scene-query flag bits");
+    if (int rc = check_query_args(n, stack_mode, 0u)) return rc;
+    if (n_objects > 0 && !objects) return fail(SVO_ERR_ARG, "null object list");
+    if (int rc = check_object_list(objects, n_objects)) return rc;
+    return check_object_roots(is_multi(ctx) ? ctx->members[0] : ctx, objects, n_objects);
+}
+
+// One scene query on context c (single-device), its device selected: arguments checked by the caller.
+int scene_device(svo_ctx *c, const svo_ray *d_rays, size_t n, int stack_mode, uint32_t flags, const svo_object *objects,
+                 int n_objects, const svo_query_out &out, int32_t *d_object, hipStream_t s) {
+    if ((uintptr_t)d_rays & 15u) return fail(SVO_ERR_ARG, "d_rays must be 16-byte aligned");
+    svo::LaunchParams p;
+    std::memset(&p, 0, sizeof p);
+    p.nodes = c->d_nodes;
+    p.att = c->d_att;
+    p.n_nodes = (uint32_t)std::min<size_t>(c->n_nodes, 0xFFFFFFFFu);
+    p.slots = 21;   // every walk of a scene query is guarded, on the full stack (svo_kernel.hip OBJECT_SLOTS)
+    p.guard = 1;
+    svo::QueryArgs q;
+    std::memset(&q, 0, sizeof q);
+    q.rays = reinterpret_cast<const svo::QueryRay *>(d_rays);
+    q.n = (uint32_t)n;
+    q.flags = (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u;
+    q.out.hits = reinterpret_cast<svo::Hit *>(out.hits);
+    q.out.position = reinterpret_cast<float4 *>(out.position);
+    q.out.voxel = reinterpret_cast<unsigned long long *>(out.voxel);
+    q.out.hitmask = reinterpret_cast<unsigned long long *>(out.hitmask);
+    svo_objects::Object obs[svo_objects::MAX_OBJECTS] = {};
+    for (int j = 0; j < n_objects; ++j) std::memcpy(obs + j, objects + j, sizeof obs[j]);
+    const hipError_t e = svo::launch_scene_query(p, q, obs, n_objects, !(flags & SVO_SCENE_NO_TERRAIN), d_object, stack_mode, s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("scene query launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
 int check_sky_args(svo_ctx *ctx, const float *dirs, size_t n, const float *rgba) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
     if (!dirs) return fail(SVO_ERR_ARG, "null direction list");
@@ -2537,6 +2663,110 @@ int svo_light_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t fl
         return SVO_OK;
     } catch (const std::exception &e) {
         return fail(SVO_ERR_HIP, std::string("svo_light_rays_host: ") + e.what());
+    }
+}
+
+int svo_object_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_object *object,
+                    svo_ray *d_rays_out, void *stream) {
+    int rc = check_object_ray_args(ctx, d_rays, n, flags, object, d_rays_out);
+    if (rc) return rc;
+    if (((uintptr_t)d_rays | (uintptr_t)d_rays_out) & 15u) return fail(SVO_ERR_ARG, "ray lists must be 16-byte aligned");
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        return object_rays_device(d_rays, n, object, d_rays_out, stream ? (hipStream_t)stream : c->stream);
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_object_rays: ") + e.what());
+    }
+}
+
+int svo_object_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_object *object,
+                         svo_ray *rays_out) {
+    int rc = check_object_ray_args(ctx, rays, n, flags, object, rays_out);
+    if (rc) return rc;
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        HIP_TRY(hipSetDevice(c->device));
+        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, 32 * n);
+        if (rc) return rc;
+        rc = order_query_scratch(c, c->stream);
+        if (rc) return rc;
+        char *base = static_cast<char *>(c->q_host);
+        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
+            hipStream_t s;
+            ~Drain() { hipStreamSynchronize(s); }
+        } drain{c->stream};
+        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
+        rc = object_rays_device(base, n, object, base, c->stream);   // in place
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(rays_out, base, 32 * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SVO_OK;
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_object_rays_host: ") + e.what());
+    }
+}
+
+int svo_trace_scene(svo_ctx *ctx, const svo_ray *d_rays, size_t n, int stack_mode, uint32_t flags,
+                    const svo_object *objects, int n_objects, const svo_query_out *out, int32_t *d_object, void *stream) {
+    const bool any_out = d_object || (out && (out->hits || out->position || out->voxel || out->hitmask));
+    int rc = check_scene_args(ctx, d_rays, n, stack_mode, flags, objects, n_objects, any_out);
+    if (rc) return rc;
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
+        HIP_TRY(hipSetDevice(c->device));
+        const svo_query_out none{};
+        return scene_device(c, d_rays, n, stack_mode, flags, objects, n_objects, out ? *out : none, d_object,
+                            stream ? (hipStream_t)stream : c->stream);
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_trace_scene: ") + e.what());
+    }
+}
+
+int svo_trace_scene_host(svo_ctx *ctx, const svo_ray *rays, size_t n, int stack_mode, uint32_t flags,
+                         const svo_object *objects, int n_objects, svo_hit *hits, float *position, uint64_t *voxel,
+                         int32_t *object) {
+    int rc = check_scene_args(ctx, rays, n, stack_mode, flags, objects, n_objects, hits || position || voxel || object);
+    if (rc) return rc;
+    if (n == 0) return SVO_OK;
+    try {
+        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
+        if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
+        HIP_TRY(hipSetDevice(c->device));
+        // staged layout: rays (32 B), positions (16 B), hit records (24 B), voxel keys (8 B), ids (4 B) per ray;
+        // every part 16-byte aligned for any n
+        const size_t off_pos = 32 * n, off_hits = 48 * n, off_vox = (72 * n + 15) & ~(size_t)15,
+                     off_id = (off_vox + 8 * n + 15) & ~(size_t)15;
+        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, off_id + 4 * n);
+        if (rc) return rc;
+        rc = order_query_scratch(c, c->stream);
+        if (rc) return rc;
+        char *base = static_cast<char *>(c->q_host);
+        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
+            hipStream_t s;
+            ~Drain() { hipStreamSynchronize(s); }
+        } drain{c->stream};
+        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
+        svo_query_out out{};
+        out.hits = hits ? reinterpret_cast<svo_hit *>(base + off_hits) : nullptr;
+        out.position = position ? reinterpret_cast<float *>(base + off_pos) : nullptr;
+        out.voxel = voxel ? reinterpret_cast<uint64_t *>(base + off_vox) : nullptr;
+        int32_t *d_object = object ? reinterpret_cast<int32_t *>(base + off_id) : nullptr;
+        rc = scene_device(c, reinterpret_cast<const svo_ray *>(base), n, stack_mode, flags, objects, n_objects, out,
+                          d_object, c->stream);
+        if (rc) return rc;
+        if (hits) HIP_TRY(hipMemcpyAsync(hits, out.hits, 24 * n, hipMemcpyDeviceToHost, c->stream));
+        if (position) HIP_TRY(hipMemcpyAsync(position, out.position, 16 * n, hipMemcpyDeviceToHost, c->stream));
+        if (voxel) HIP_TRY(hipMemcpyAsync(voxel, out.voxel, 8 * n, hipMemcpyDeviceToHost, c->stream));
+        if (object) HIP_TRY(hipMemcpyAsync(object, d_object, 4 * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        return SVO_OK;
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string("svo_trace_scene_host: ") + e.what());
     }
 }
 
@@ -2910,6 +3140,28 @@ int svo_get_lights(svo_ctx *ctx, svo_light *lights, int cap, int *n_lights) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
     for (int j = 0; lights && j < cap && j < ctx->n_lights; ++j) std::memcpy(lights + j, ctx->lights + j, sizeof(svo_light));
     if (n_lights) *n_lights = ctx->n_lights;
+    return SVO_OK;
+}
+
+int svo_set_objects(svo_ctx *ctx, const svo_object *objects, int n_objects) {
+    if (int rc = check_object_list(objects, n_objects)) return rc;   // before the context is read
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    const int n = objects ? n_objects : 0;
+    if (n > 0 && is_multi(ctx)) return fail(SVO_ERR_STATE, "objects on a multi-device context are not supported");
+    if (int rc = check_object_roots(ctx, objects, n)) return rc;
+    for (int j = 0; j < svo_objects::MAX_OBJECTS; ++j) {
+        svo_objects::Object ob{};
+        if (j < n) std::memcpy(&ob, objects + j, sizeof ob);
+        ctx->objects[j] = ob;
+    }
+    ctx->n_objects = n;
+    return SVO_OK;
+}
+
+int svo_get_objects(svo_ctx *ctx, svo_object *objects, int cap, int *n_objects) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    for (int j = 0; objects && j < cap && j < ctx->n_objects; ++j) std::memcpy(objects + j, ctx->objects + j, sizeof(svo_object));
+    if (n_objects) *n_objects = ctx->n_objects;
     return SVO_OK;
 }
 

@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "svo_light.h"
+#include "svo_object.h"
 #include "svo_sky.h"
 
 namespace svo {
@@ -363,5 +364,24 @@ hipError_t launch_ambient_rays(const QueryRay *rays, uint32_t n, uint32_t flags,
 hipError_t launch_light_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
                              const unsigned long long *voxel, const svo_lights::Light *lights, int n_lights, QueryRay *out,
                              hipStream_t stream);
+
+// Scene objects (svo_set_objects, svo_trace_scene; svo_object.h is the rule).  `objects`
+// is a host array of 0 .. 8 valid objects whose roots lie inside the pool's capacity; it travels as a
+// kernel argument.  Every walk runs the guarded loop on its own 21-slot stack, whatever p.guard / p.slots say.
+// svo_object_rays: out[i] = rays[i] in the object's frame before the clamp, or the dead ray.  A flat launch,
+// one thread per ray; out may be rays.
+hipError_t launch_object_rays(const QueryRay *rays, uint32_t n, const svo_objects::Object &object, QueryRay *out,
+                              hipStream_t stream);
+// svo_trace_scene: launch_query's p and q (q.index null: no ordered mode); per ray the nearest hit among the
+// terrain (root 0; skipped with terrain false) and the objects, and its id (object_id, nullable: -1 miss,
+// 0 terrain, j + 1 object j).
+hipError_t launch_scene_query(const LaunchParams &p, const QueryArgs &q, const svo_objects::Object *objects, int n_objects,
+                              bool terrain, int32_t *object_id, int stack_mode, hipStream_t stream);
+// Object pass behind a render launch's primary rays (object_pass_kernel): one wave64 per 8x8 tile of the
+// launch's rows.  p: the launch's own parameters; out.hits or out.compact hold the primary records, and a
+// pixel where an object is nearer gets every non-null output rewritten and its bit set in out.hitmask
+// (nullable).  n_objects 1 .. 8.
+hipError_t launch_objects(const LaunchParams &p, const svo_objects::Object *objects, int n_objects, int stack_mode,
+                          hipStream_t stream);
 
 }  // namespace svo

@@ -227,6 +227,27 @@ class RaytracingMaster:
         check(_lib.lib().svo_get_lights(self._ctx, out.ctypes.data, _lib.MAX_LIGHTS, ctypes.byref(n)), "svo_get_lights")
         return out[:n.value].copy()
 
+    def SetObjects(self, objects):
+        """Placed sub-SVOs of the renders (svo_set_objects; objects.py is the rule): up to 8 objects, each
+        (root, scale_log2, position, rotation[, flags]) or an OBJECT_DTYPE record; None or an empty list: off,
+        the default.  root: the descriptor index of a tree uploaded behind the terrain (SetSVOBuffer with an
+        offset); the object's cube has side 32 * 2^scale_log2 world units, centred at position, rotated by
+        the row-major rotation (world = R * object).  A pixel where an object is nearer than the terrain
+        gets the object's record (world normal, object-local position and key) and colour."""
+        from .objects import make_objects
+        before = self.GetObjects().tobytes()
+        rec = make_objects(objects if objects is not None else [])
+        check(_lib.lib().svo_set_objects(self._ctx, rec.ctypes.data if len(rec) else None, len(rec)), "svo_set_objects")
+        if self.GetObjects().tobytes() != before:   # another image: the accumulation restarts
+            self.currentSample = 0
+
+    def GetObjects(self):
+        """The context's objects (svo_get_objects): OBJECT_DTYPE [n]."""
+        n = ctypes.c_int()
+        out = np.zeros(_lib.MAX_OBJECTS, _lib.OBJECT_DTYPE)
+        check(_lib.lib().svo_get_objects(self._ctx, out.ctypes.data, _lib.MAX_OBJECTS, ctypes.byref(n)), "svo_get_objects")
+        return out[:n.value].copy()
+
     def SetSkybox(self, texels, bilinear=True, clamp_v=False):
         """~ RayTracingShader.SetTexture(0, "_SkyboxTexture", SkyboxTexture) (RaytracingMaster.cs:28;
         svo_set_skybox): an equirectangular panorama for the rays that leave the scene.  texels: H x W x 4
@@ -596,6 +617,63 @@ class RaytracingMaster:
         rec = make_lights(lights)
         check(_lib.lib().svo_light_rays(self._ctx, rays_ptr, int(n), self._query_flags(False, raw), hits, voxel,
                                         rec.ctypes.data, len(rec), out, stream), "svo_light_rays")
+
+    def ObjectRays(self, rays, obj):
+        """A batch of world rays in an object's frame (svo_object_rays_host; objects.object_rays is its numpy
+        statement): rays RAY_DTYPE [n], obj one object (make_objects' forms).  Returns RAY_DTYPE [n]: {o',
+        t_max, d', 0} before the small-direction clamp, a dead ray where the world ray is invalid."""
+        from .objects import make_objects
+        rays = np.ascontiguousarray(rays, _lib.RAY_DTYPE).reshape(-1)
+        rec = make_objects(obj if isinstance(obj, (list, np.ndarray)) else [obj])
+        if len(rec) != 1:
+            raise ValueError(f"one object expected, {len(rec)} given")
+        out = np.zeros(len(rays), _lib.RAY_DTYPE)
+        check(_lib.lib().svo_object_rays_host(self._ctx, rays.ctypes.data, len(rays), 0, rec.ctypes.data,
+                                              out.ctypes.data), "svo_object_rays_host")
+        return out
+
+    def object_rays_device(self, rays_ptr, n, out, obj, stream=None):
+        """Asynchronous svo_object_rays on device buffers: rays_ptr / out = n svo_ray records (16-byte
+        aligned; out may be rays_ptr); obj: one host record (the call copies it before it returns)."""
+        from .objects import make_objects
+        rec = make_objects(obj if isinstance(obj, (list, np.ndarray)) else [obj])
+        check(_lib.lib().svo_object_rays(self._ctx, rays_ptr, int(n), 0, rec.ctypes.data, out, stream), "svo_object_rays")
+
+    def TraceScene(self, rays, objects=(), stack_mode=STACK_HLSL, raw=False, terrain=True, want_position=False,
+                   want_voxel=False):
+        """Trace a batch of world rays through the terrain (root 0) and placed objects (svo_trace_scene_host;
+        objects.py is the rule): rays RAY_DTYPE [n], objects up to 8 (make_objects' forms; the context's own
+        list, SetObjects, is not involved).  terrain=False: SVO_SCENE_NO_TERRAIN.  Blocking.  Returns (hits,
+        object_id) or (hits, object_id, position or None, voxel or None): the nearest hit per ray with its
+        normal in world space, t / 64 the world ray's parameter, position and voxel key object-local, parent
+        the absolute pool index; object_id int32 [n]: -1 a miss, 0 the terrain, j + 1 object j."""
+        from .objects import make_objects
+        rays = np.ascontiguousarray(rays, _lib.RAY_DTYPE).reshape(-1)
+        rec = make_objects(objects if objects is not None else [])
+        n = len(rays)
+        hits = np.zeros(n, HIT_DTYPE)
+        ids = np.zeros(n, np.int32)
+        pos = np.zeros((n, 4), np.float32) if want_position else None
+        vox = np.zeros(n, np.uint64) if want_voxel else None
+        flags = self._query_flags(False, raw) | (0 if terrain else _lib.SCENE_NO_TERRAIN)
+        check(_lib.lib().svo_trace_scene_host(self._ctx, rays.ctypes.data, n, stack_mode, flags,
+                                              rec.ctypes.data if len(rec) else None, len(rec), hits.ctypes.data,
+                                              None if pos is None else pos.ctypes.data,
+                                              None if vox is None else vox.ctypes.data, ids.ctypes.data),
+              "svo_trace_scene_host")
+        return (hits, ids, pos, vox) if (want_position or want_voxel) else (hits, ids)
+
+    def trace_scene_device(self, rays_ptr, n, objects=(), hits=None, position=None, voxel=None, hitmask=None,
+                           object_id=None, stack_mode=STACK_HLSL, raw=False, terrain=True, stream=None):
+        """Asynchronous svo_trace_scene on device buffers: trace_rays_device's buffers plus object_id (n int32,
+        nullable); objects: host records (the call copies them before it returns)."""
+        from .objects import make_objects
+        rec = make_objects(objects if objects is not None else [])
+        out = _lib.SvoQueryOut(hits, position, voxel, hitmask)
+        flags = self._query_flags(False, raw) | (0 if terrain else _lib.SCENE_NO_TERRAIN)
+        check(_lib.lib().svo_trace_scene(self._ctx, rays_ptr, int(n), stack_mode, flags,
+                                         rec.ctypes.data if len(rec) else None, len(rec), ctypes.byref(out), object_id,
+                                         stream), "svo_trace_scene")
 
     def beam_starts_device(self, width, height, starts_ptr, band=None, stream=None):
         """svo_beam_starts: every primary ray's beam start (SVO-space t, -inf: the cube entry) into a

@@ -128,6 +128,32 @@ public static class SvoNative {
     [DllImport(Lib)] public static extern int svo_light_rays_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr n, uint flags,
                                                                   [In] SvoHit[] hits, [In] ulong[] voxel,
                                                                   [In] SvoLight[] lights, int nLights, [Out] SvoRay[] raysOut);
+    // Objects (svo_rt.h): sub-SVOs of the pool placed in the world -- the renders' list and the scene query
+    public const int MaxObjects = 8;
+    public const uint SceneNoTerrain = 4;
+    [Serializable]
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoObject {         // svo_object, 64 bytes
+        public uint root;             // descriptor index of the object's root in the pool
+        public int scaleLog2;         // k in [-8, 8]: the cube has side 32 * 2^k world units
+        public uint flags;            // 0
+        public Vector3 position;      // world position of the cube's centre, |component| <= 2^20
+        public float r00, r01, r02, r10, r11, r12, r20, r21, r22;   // row-major R, world = R * object
+        public uint reserved;         // 0
+    }
+    [DllImport(Lib)] public static extern int svo_set_objects(IntPtr ctx, [In] SvoObject[] objects, int nObjects);
+    [DllImport(Lib)] public static extern int svo_get_objects(IntPtr ctx, [Out] SvoObject[] objects, int cap, out int nObjects);
+    [DllImport(Lib)] public static extern int svo_object_rays(IntPtr ctx, IntPtr dRays, UIntPtr n, uint flags,
+                                                              [In] ref SvoObject obj, IntPtr dRaysOut, IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_object_rays_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr n, uint flags,
+                                                                   [In] ref SvoObject obj, [Out] SvoRay[] raysOut);
+    [DllImport(Lib)] public static extern int svo_trace_scene(IntPtr ctx, IntPtr dRays, UIntPtr n, int stackMode, uint flags,
+                                                              [In] SvoObject[] objects, int nObjects, IntPtr queryOut,
+                                                              IntPtr dObject, IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_trace_scene_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr n, int stackMode,
+                                                                   uint flags, [In] SvoObject[] objects, int nObjects,
+                                                                   [Out] SvoHit[] hits, [Out] Vector4[] position,
+                                                                   [Out] ulong[] voxel, [Out] int[] objectId);
     // Skybox (svo_rt.h): the reference's _SkyboxTexture for rays that leave the scene, and its rule for ray queries
     public const uint SkyBilinear = 1, SkyClampV = 2;
     [DllImport(Lib)] public static extern int svo_set_skybox(IntPtr ctx, [In] Color[] rgba, int width, int height, uint flags);
@@ -428,6 +454,36 @@ public class RaytracingMasterNative : MonoBehaviour {
             rec[j].flags = shadows && pointLights[j].shadows != LightShadows.None ? 0u : SvoNative.LightNoShadow;
         }
         SvoNative.Check(SvoNative.svo_set_lights(_ctx, n > 0 ? rec : null, n), "svo_set_lights");
+        _currentSample = 0;   // another image: a fresh accumulation
+    }
+
+    // A voxel model placed on the voxel world (svo_set_objects): its tree was uploaded behind the terrain at
+    // descriptor index `root`; the Transform gives the placement.  Serialisable, so a scene keeps its list.
+    [Serializable]
+    public struct PlacedObject {
+        public uint root;             // where the model's tree lies in the pool
+        public int scaleLog2;         // the cube's side is 32 * 2^scaleLog2 world units
+        public Transform transform;   // position and rotation (its scale is not read: uniform powers of two only)
+    }
+    public PlacedObject[] placedObjects;
+
+    // The placed objects of the renders (svo_set_objects; it changes the image): up to 8.  Call it whenever one
+    // moves; null or an empty array turns them off.  Not supported together with shadow rays, specular,
+    // lodPixels, ambient, lights or gpus > 1.
+    public void SetObjects(PlacedObject[] objects) {
+        int n = objects == null ? 0 : Mathf.Min(objects.Length, SvoNative.MaxObjects);
+        var rec = new SvoNative.SvoObject[n];
+        for (int j = 0; j < n; ++j) {
+            Matrix4x4 m = Matrix4x4.Rotate(objects[j].transform.rotation);
+            rec[j].root = objects[j].root;
+            rec[j].scaleLog2 = objects[j].scaleLog2;
+            rec[j].position = objects[j].transform.position;
+            rec[j].r00 = m.m00; rec[j].r01 = m.m01; rec[j].r02 = m.m02;
+            rec[j].r10 = m.m10; rec[j].r11 = m.m11; rec[j].r12 = m.m12;
+            rec[j].r20 = m.m20; rec[j].r21 = m.m21; rec[j].r22 = m.m22;
+        }
+        SvoNative.Check(SvoNative.svo_set_objects(_ctx, n > 0 ? rec : null, n), "svo_set_objects");
+        placedObjects = objects;
         _currentSample = 0;   // another image: a fresh accumulation
     }
 
