@@ -23,8 +23,8 @@ import re
 
 import numpy as np
 
-from ._lib import HIT_DTYPE, PKG_DIR, RAY_DTYPE
-from .query import sanitize_rays
+from ._lib import PKG_DIR
+from .query import batch_arrays, sanitize_rays
 from .reflection import dead_rays, entry_face
 
 COUNTS = (4, 8, 16)
@@ -76,11 +76,7 @@ def ambient_rays(rays, hits, voxel, n_rays=4, radius=np.inf, variant=0, raw=Fals
     (HIT_DTYPE) has flag bit 0, else the dead ray.  voxel: the hits' voxel keys (uint64).  raw: rays
     were traced with SVO_QUERY_RAW_DIRECTIONS (no small-direction clamp)."""
     f = np.float32
-    rays = np.ascontiguousarray(rays, RAY_DTYPE).reshape(-1)
-    hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
-    voxel = np.ascontiguousarray(voxel, np.uint64).reshape(-1)
-    if not len(rays) == len(hits) == len(voxel):
-        raise ValueError(f"{len(rays)} rays, {len(hits)} hit records, {len(voxel)} voxel keys")
+    rays, hits, voxel = batch_arrays(rays, hits, voxel)
     if not (radius > 0):
         raise ValueError(f"radius must be +inf or finite and positive, got {radius}")
     tab = variant_table(n_rays, variant)

@@ -407,8 +407,8 @@ struct svo_ctx {
     size_t q_cap = 0;
     void *q_temp = nullptr;
     size_t q_temp_cap = 0;
-    void *q_host = nullptr;              // rays, hits, positions, voxel keys of q_host_cap rays
-    size_t q_host_cap = 0;
+    void *q_host = nullptr;              // device staging of the _host ray-batch calls (HostStage lays out the parts)
+    size_t q_host_cap = 0;               // its size in bytes
     hipStream_t q_stream = nullptr;
     bool q_valid = false;
     hipEvent_t q_event = nullptr;
@@ -2146,6 +2146,10 @@ int apply_config(svo_ctx *c, const svo_config &k) {
 }
 
 // ------------------------------------------------------------------ ray queries
+// The ray-batch calls (svo_trace_rays .. svo_sample_sky and their _host twins) share four pieces: HostStage
+// (the staged round trip of a _host call), on_device (the entry shell), the check_batch_* argument checks and
+// the launch-struct fillers pool_params / query_args / batch_of.  DESIGN.md 3.2i.
+
 // Make stream s wait for the query-scratch work the previous user enqueued on another stream
 // (order_scratch's rule, for the query's own scratch).
 int order_query_scratch(svo_ctx *c, hipStream_t s) {
@@ -2167,13 +2171,92 @@ int grow_query_scratch(T **buf, size_t *cap, size_t need) {
     return regrow(buf, cap, need, need);
 }
 
+// The staged round trip of a _host call, on the context's stream and its host-staging scratch: reserve the
+// parts, begin(), upload, the launch, download, finish().  The rule it exists for: no copy may still read or
+// write the caller's arrays once the call has returned, an error included -- so from begin() on, every exit
+// but finish() waits for the stream in the destructor, and finish() is the wait whose error is reported.
+class HostStage {
+public:
+    explicit HostStage(svo_ctx *c) : c_(c) {}
+    HostStage(const HostStage &) = delete;
+    HostStage &operator=(const HostStage &) = delete;
+    ~HostStage() {
+        if (armed_) hipStreamSynchronize(c_->stream);
+    }
+    // Reserve `bytes` before begin(): the part's offset.  Every part starts on a 16-byte boundary, the
+    // strictest alignment a kernel asks of a list.
+    size_t part(size_t bytes) {
+        const size_t offset = size_;
+        size_ = (offset + bytes + 15) & ~(size_t)15;
+        return offset;
+    }
+    int begin() {
+        if (int rc = grow_query_scratch(&c_->q_host, &c_->q_host_cap, size_)) return rc;
+        if (int rc = order_query_scratch(c_, c_->stream)) return rc;
+        armed_ = true;
+        return SVO_OK;
+    }
+    // A part's device pointer (after begin()).
+    template <class T = void>
+    T *at(size_t part) const {
+        return reinterpret_cast<T *>(static_cast<char *>(c_->q_host) + part);
+    }
+    // The part's pointer if the caller has this list (an optional input or output), else null.
+    template <class T = void>
+    T *at_if(const void *wanted, size_t part) const {
+        return wanted ? at<T>(part) : nullptr;
+    }
+    // A null src or dst is a list the caller does not have: no copy.
+    int upload(size_t part, const void *src, size_t bytes) {
+        if (src) HIP_TRY(hipMemcpyAsync(at(part), src, bytes, hipMemcpyHostToDevice, c_->stream));
+        return SVO_OK;
+    }
+    int download(void *dst, size_t part, size_t bytes) {
+        if (dst) HIP_TRY(hipMemcpyAsync(dst, at(part), bytes, hipMemcpyDeviceToHost, c_->stream));
+        return SVO_OK;
+    }
+    int finish() {
+        HIP_TRY(hipStreamSynchronize(c_->stream));
+        armed_ = false;
+        return SVO_OK;
+    }
+
+private:
+    svo_ctx *c_;
+    size_t size_ = 0;
+    bool armed_ = false;
+};
+
+svo_ctx *batch_context(svo_ctx *ctx) { return is_multi(ctx) ? ctx->members[0] : ctx; }
+
+// The shell of every ray-batch entry point once its arguments are checked: a multi-device context's member 0,
+// the pool test where the call walks the pool (before a device is selected), the device, the stream (null:
+// the context's own), and body(c, s) with what it throws reported under the entry point's name.
+template <class F>
+int on_device(svo_ctx *ctx, const char *name, void *stream, bool needs_pool, F &&body) {
+    try {
+        svo_ctx *c = batch_context(ctx);
+        if (needs_pool && c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
+        HIP_TRY(hipSetDevice(c->device));
+        return body(c, stream ? (hipStream_t)stream : c->stream);
+    } catch (const std::exception &e) {
+        return fail(SVO_ERR_HIP, std::string(name) + ": " + e.what());
+    }
+}
+
+// A launch's result, or SVO_ERR_HIP under `label`.
+int launched(hipError_t e, const char *label) {
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string(label) + ": " + hipGetErrorString(e));
+    return SVO_OK;
+}
+
 constexpr size_t MAX_QUERY_RAYS = ((size_t)1 << 31) - 1;
 
 // A LOD pair (svo_set_lod, svo_trace_rays_lod): two non-negative finite numbers (-0 counts as 0).
 bool lod_pair_ok(float coef, float bias) { return std::isfinite(coef) && std::isfinite(bias) && coef >= 0.0f && bias >= 0.0f; }
 const char *const LOD_PAIR_MSG = "ray_size_coef and ray_size_bias must be finite and not negative";
 
-// The argument checks of both entry points that need no device and no context state.
+// ---- the argument checks that need no device and no context state
 int check_query_args(size_t n_rays, int stack_mode, uint32_t flags) {
     if (flags & ~(uint32_t)(SVO_QUERY_ORDERED | SVO_QUERY_RAW_DIRECTIONS)) return fail(SVO_ERR_ARG, "unknown query flag bits");
     if (stack_mode != SVO_STACK_HLSL && stack_mode != SVO_STACK_EXACT) return fail(SVO_ERR_ARG, "unknown stack mode");
@@ -2181,16 +2264,115 @@ int check_query_args(size_t n_rays, int stack_mode, uint32_t flags) {
     return SVO_OK;
 }
 
-// One query on context c (single-device), its device selected: arguments checked by the caller.
-int query_device(svo_ctx *c, const svo_ray *d_rays, size_t n_rays, int stack_mode, uint32_t flags,
-                 const svo_query_out &out, hipStream_t s, float lod_coef, float lod_bias) {
-    if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
-    if ((uintptr_t)d_rays & 15u) return fail(SVO_ERR_ARG, "d_rays must be 16-byte aligned");
+// The head of the calls on a traced batch (bounce, ambient, light rays): the pointers, then the flags, with
+// the call's own word in the complaint.
+int check_batch_head(const svo_ctx *ctx, const void *rays, const void *hits, const void *voxel, const void *rays_out,
+                     uint32_t flags, const char *word) {
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!rays) return fail(SVO_ERR_ARG, "null ray list");
+    if (!hits) return fail(SVO_ERR_ARG, "null hit records");
+    if (!voxel) return fail(SVO_ERR_ARG, "null voxel keys");
+    if (!rays_out) return fail(SVO_ERR_ARG, "null output ray list");
+    if (flags & ~(uint32_t)SVO_QUERY_RAW_DIRECTIONS) return fail(SVO_ERR_ARG, std::string("unknown ") + word + " flag bits");
+    return SVO_OK;
+}
+
+// n entries with `fan` output rays each: at most 2^31 - 1 of `what`.
+int check_batch_count(size_t n, size_t fan, const char *what) {
+    if (n > MAX_QUERY_RAYS / fan) return fail(SVO_ERR_ARG, std::string("more than 2^31 - 1 ") + what + " in one batch");
+    return SVO_OK;
+}
+
+bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+// The tail of the calls that fan out (ambient, light rays): the count, then the output list clear of every
+// input.  Not for the calls that may work in place (bounce, object rays: check_batch_count alone).
+int check_batch_fan(const void *rays, size_t n, const void *hits, const void *voxel, size_t fan, const void *rays_out,
+                    const char *what) {
+    if (int rc = check_batch_count(n, fan, what)) return rc;
+    const size_t out_bytes = 32 * n * fan;
+    if (ranges_overlap(rays_out, out_bytes, rays, 32 * n) || ranges_overlap(rays_out, out_bytes, hits, 24 * n) ||
+        ranges_overlap(rays_out, out_bytes, voxel, 8 * n))
+        return fail(SVO_ERR_ARG, "the output ray list overlaps an input");
+    return SVO_OK;
+}
+
+// The device pointers' alignment (null where the call has no such list).
+int check_batch_alignment(const void *d_rays, const void *d_rays_out, const void *d_hits, const void *d_voxel) {
+    if (((uintptr_t)d_rays | (uintptr_t)d_rays_out) & 15u) return fail(SVO_ERR_ARG, "ray lists must be 16-byte aligned");
+    if (((uintptr_t)d_hits | (uintptr_t)d_voxel) & 7u) return fail(SVO_ERR_ARG, "hit records and voxel keys must be 8-byte aligned");
+    return SVO_OK;
+}
+
+// ---- the launch structs
+uint32_t raw_bit(uint32_t flags) { return (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u; }
+
+svo::LaunchParams pool_params(const svo_ctx *c) {
     svo::LaunchParams p;
     std::memset(&p, 0, sizeof p);
     p.nodes = c->d_nodes;
     p.att = c->d_att;
     p.n_nodes = (uint32_t)std::min<size_t>(c->n_nodes, 0xFFFFFFFFu);
+    return p;
+}
+
+svo::QueryArgs query_args(const svo_ray *d_rays, size_t n, uint32_t flags, const svo_query_out &out) {
+    svo::QueryArgs q;
+    std::memset(&q, 0, sizeof q);
+    q.rays = reinterpret_cast<const svo::QueryRay *>(d_rays);
+    q.n = (uint32_t)n;
+    q.flags = raw_bit(flags);
+    q.out.hits = reinterpret_cast<svo::Hit *>(out.hits);
+    q.out.position = reinterpret_cast<float4 *>(out.position);
+    q.out.voxel = reinterpret_cast<unsigned long long *>(out.voxel);
+    q.out.hitmask = reinterpret_cast<unsigned long long *>(out.hitmask);
+    return q;
+}
+
+// A traced batch as the flat kernels take it (bounce, ambient, light and object rays; hits and voxel null
+// where the call has none).
+struct Batch {
+    const svo::QueryRay *rays;
+    uint32_t n, raw;
+    const svo::Hit *hits;
+    const unsigned long long *voxel;
+    svo::QueryRay *out;
+};
+
+Batch batch_of(const void *d_rays, size_t n, uint32_t flags, const void *d_hits, const void *d_voxel, void *d_rays_out) {
+    return {static_cast<const svo::QueryRay *>(d_rays), (uint32_t)n, raw_bit(flags), static_cast<const svo::Hit *>(d_hits),
+            static_cast<const unsigned long long *>(d_voxel), static_cast<svo::QueryRay *>(d_rays_out)};
+}
+
+int bounce_launch(const Batch &b, hipStream_t s) {
+    return launched(svo::launch_bounce_rays(b.rays, b.n, b.raw, b.hits, b.voxel, b.out, s), "bounce launch");
+}
+
+int ambient_launch(const Batch &b, int n_rays, float radius, uint32_t variant, hipStream_t s) {
+    return launched(svo::launch_ambient_rays(b.rays, b.n, b.raw, b.hits, b.voxel, n_rays, radius, variant, b.out, s),
+                    "ambient ray launch");
+}
+
+int light_launch(const Batch &b, const svo_light *lights, int n_lights, hipStream_t s) {
+    return launched(svo::launch_light_rays(b.rays, b.n, b.raw, b.hits, b.voxel,
+                                           reinterpret_cast<const svo_lights::Light *>(lights), n_lights, b.out, s),
+                    "light ray launch");
+}
+
+int object_rays_launch(const Batch &b, const svo_object *object, hipStream_t s) {
+    svo_objects::Object ob;
+    std::memcpy(&ob, object, sizeof ob);
+    return launched(svo::launch_object_rays(b.rays, b.n, ob, b.out, s), "object ray launch");
+}
+
+// One query on context c (single-device), its device selected: arguments and pool checked by the caller.
+int query_device(svo_ctx *c, const svo_ray *d_rays, size_t n_rays, int stack_mode, uint32_t flags,
+                 const svo_query_out &out, hipStream_t s, float lod_coef, float lod_bias) {
+    if ((uintptr_t)d_rays & 15u) return fail(SVO_ERR_ARG, "d_rays must be 16-byte aligned");
+    svo::LaunchParams p = pool_params(c);
     // loop form: exactly the render launch's choice for this pool (launch): guarded unless the
     // longest path is proven (at most 22 levels, no cycle) and the parent indices are exact
     p.slots = std::max(c->depth - 1, 1);
@@ -2200,15 +2382,7 @@ int query_device(svo_ctx *c, const svo_ray *d_rays, size_t n_rays, int stack_mod
     p.lod = lod_coef != 0.0f || lod_bias != 0.0f;
     p.lod_coef = lod_coef;
     p.lod_bias = lod_bias;
-    svo::QueryArgs q;
-    std::memset(&q, 0, sizeof q);
-    q.rays = reinterpret_cast<const svo::QueryRay *>(d_rays);
-    q.n = (uint32_t)n_rays;
-    q.flags = (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u;
-    q.out.hits = reinterpret_cast<svo::Hit *>(out.hits);
-    q.out.position = reinterpret_cast<float4 *>(out.position);
-    q.out.voxel = reinterpret_cast<unsigned long long *>(out.voxel);
-    q.out.hitmask = reinterpret_cast<unsigned long long *>(out.hitmask);
+    svo::QueryArgs q = query_args(d_rays, n_rays, flags, out);
     if (flags & SVO_QUERY_ORDERED) {
         const size_t temp = svo::query_sort_bytes(q.n);
         if (temp == 0) return fail(SVO_ERR_HIP, "radix sort: temporary storage query failed");
@@ -2221,36 +2395,28 @@ int query_device(svo_ctx *c, const svo_ray *d_rays, size_t n_rays, int stack_mod
         uint32_t *keys = c->q_keys, *keys_out = keys + n_rays, *index = keys + 2 * n_rays, *index_out = keys + 3 * n_rays;
         hipError_t e = svo::launch_query_keys(q, keys, index, s);
         if (e == hipSuccess) e = svo::launch_query_sort(keys, keys_out, index, index_out, q.n, c->q_temp, temp, s);
-        if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("query order: ") + hipGetErrorString(e));
+        rc = launched(e, "query order");
+        if (rc) return rc;
         q.index = index_out;
     }
-    const hipError_t e = svo::launch_query(p, q, stack_mode, s);
-    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("query launch: ") + hipGetErrorString(e));
-    return SVO_OK;
+    return launched(svo::launch_query(p, q, stack_mode, s), "query launch");
 }
 
-// The argument checks of svo_bounce_rays(_host) that need no device.
-int check_bounce_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const void *hits, const void *voxel,
-                             const void *rays_out) {
+// The checks svo_trace_rays_lod and its _host twin share.  out_error: the twin's complaint about its outputs,
+// or null.
+int check_trace_args(svo_ctx *ctx, const void *rays, size_t n_rays, int stack_mode, uint32_t flags, float lod_coef,
+                     float lod_bias, const char *out_error) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!lod_pair_ok(lod_coef, lod_bias)) return fail(SVO_ERR_ARG, LOD_PAIR_MSG);
     if (!rays) return fail(SVO_ERR_ARG, "null ray list");
-    if (!hits) return fail(SVO_ERR_ARG, "null hit records");
-    if (!voxel) return fail(SVO_ERR_ARG, "null voxel keys");
-    if (!rays_out) return fail(SVO_ERR_ARG, "null output ray list");
-    if (flags & ~(uint32_t)SVO_QUERY_RAW_DIRECTIONS) return fail(SVO_ERR_ARG, "unknown bounce flag bits");
-    if (n > MAX_QUERY_RAYS) return fail(SVO_ERR_ARG, "more than 2^31 - 1 rays in one batch");
-    return SVO_OK;
+    if (out_error) return fail(SVO_ERR_ARG, out_error);
+    return check_query_args(n_rays, stack_mode, flags);
 }
 
-int bounce_device(const void *d_rays, size_t n, uint32_t flags, const void *d_hits, const void *d_voxel,
-                         void *d_rays_out, hipStream_t s) {
-    const hipError_t e = svo::launch_bounce_rays(reinterpret_cast<const svo::QueryRay *>(d_rays), (uint32_t)n,
-                                                 (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u,
-                                                 reinterpret_cast<const svo::Hit *>(d_hits),
-                                                 reinterpret_cast<const unsigned long long *>(d_voxel),
-                                                 reinterpret_cast<svo::QueryRay *>(d_rays_out), s);
-    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("bounce launch: ") + hipGetErrorString(e));
-    return SVO_OK;
+int check_bounce_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const void *hits, const void *voxel,
+                      const void *rays_out) {
+    if (int rc = check_batch_head(ctx, rays, hits, voxel, rays_out, flags, "bounce")) return rc;
+    return check_batch_count(n, 1, "rays");   // no overlap test: rays_out may be rays
 }
 
 const char *ambient_setting_error(int n_rays, float radius, uint32_t variant) {
@@ -2260,38 +2426,11 @@ const char *ambient_setting_error(int n_rays, float radius, uint32_t variant) {
     return nullptr;
 }
 
-bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
-    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
-}
-
-// The argument checks of svo_ambient_rays(_host) that need no device.
 int check_ambient_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const void *hits, const void *voxel,
                        int n_rays, float radius, uint32_t variant, const void *rays_out) {
-    if (!ctx) return fail(SVO_ERR_ARG, "null context");
-    if (!rays) return fail(SVO_ERR_ARG, "null ray list");
-    if (!hits) return fail(SVO_ERR_ARG, "null hit records");
-    if (!voxel) return fail(SVO_ERR_ARG, "null voxel keys");
-    if (!rays_out) return fail(SVO_ERR_ARG, "null output ray list");
-    if (flags & ~(uint32_t)SVO_QUERY_RAW_DIRECTIONS) return fail(SVO_ERR_ARG, "unknown ambient flag bits");
+    if (int rc = check_batch_head(ctx, rays, hits, voxel, rays_out, flags, "ambient")) return rc;
     if (const char *msg = ambient_setting_error(n_rays, radius, variant)) return fail(SVO_ERR_ARG, msg);
-    if (n > MAX_QUERY_RAYS / (size_t)n_rays) return fail(SVO_ERR_ARG, "more than 2^31 - 1 ambient rays in one batch");
-    const size_t out_bytes = 32 * n * (size_t)n_rays;
-    if (ranges_overlap(rays_out, out_bytes, rays, 32 * n) || ranges_overlap(rays_out, out_bytes, hits, 24 * n) ||
-        ranges_overlap(rays_out, out_bytes, voxel, 8 * n))
-        return fail(SVO_ERR_ARG, "the output ray list overlaps an input");
-    return SVO_OK;
-}
-
-int ambient_device(const void *d_rays, size_t n, uint32_t flags, const void *d_hits, const void *d_voxel, int n_rays,
-                   float radius, uint32_t variant, void *d_rays_out, hipStream_t s) {
-    const hipError_t e = svo::launch_ambient_rays(reinterpret_cast<const svo::QueryRay *>(d_rays), (uint32_t)n,
-                                                  (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u,
-                                                  reinterpret_cast<const svo::Hit *>(d_hits),
-                                                  reinterpret_cast<const unsigned long long *>(d_voxel), n_rays, radius,
-                                                  variant, reinterpret_cast<svo::QueryRay *>(d_rays_out), s);
-    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("ambient ray launch: ") + hipGetErrorString(e));
-    return SVO_OK;
+    return check_batch_fan(rays, n, hits, voxel, (size_t)n_rays, rays_out, "ambient rays");
 }
 
 // A light list as svo_set_lights and svo_light_rays take it (host memory): n_lights in 0 .. 8, and with a
@@ -2307,36 +2446,13 @@ int check_light_list(const svo_light *lights, int n_lights) {
     return SVO_OK;
 }
 
-// The argument checks of svo_light_rays(_host) that need no device.
 int check_light_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const void *hits, const void *voxel,
                      const svo_light *lights, int n_lights, const void *rays_out) {
-    if (!ctx) return fail(SVO_ERR_ARG, "null context");
-    if (!rays) return fail(SVO_ERR_ARG, "null ray list");
-    if (!hits) return fail(SVO_ERR_ARG, "null hit records");
-    if (!voxel) return fail(SVO_ERR_ARG, "null voxel keys");
-    if (!rays_out) return fail(SVO_ERR_ARG, "null output ray list");
-    if (flags & ~(uint32_t)SVO_QUERY_RAW_DIRECTIONS) return fail(SVO_ERR_ARG, "unknown light-ray flag bits");
+    if (int rc = check_batch_head(ctx, rays, hits, voxel, rays_out, flags, "light-ray")) return rc;
     if (!lights) return fail(SVO_ERR_ARG, "null light list");
     if (n_lights < 1) return fail(SVO_ERR_ARG, "n_lights must lie in 1..8");
     if (int rc = check_light_list(lights, n_lights)) return rc;
-    if (n > MAX_QUERY_RAYS / (size_t)n_lights) return fail(SVO_ERR_ARG, "more than 2^31 - 1 light rays in one batch");
-    const size_t out_bytes = 32 * n * (size_t)n_lights;
-    if (ranges_overlap(rays_out, out_bytes, rays, 32 * n) || ranges_overlap(rays_out, out_bytes, hits, 24 * n) ||
-        ranges_overlap(rays_out, out_bytes, voxel, 8 * n))
-        return fail(SVO_ERR_ARG, "the output ray list overlaps an input");
-    return SVO_OK;
-}
-
-int light_device(const void *d_rays, size_t n, uint32_t flags, const void *d_hits, const void *d_voxel,
-                 const svo_light *lights, int n_lights, void *d_rays_out, hipStream_t s) {
-    const hipError_t e = svo::launch_light_rays(reinterpret_cast<const svo::QueryRay *>(d_rays), (uint32_t)n,
-                                                (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u,
-                                                reinterpret_cast<const svo::Hit *>(d_hits),
-                                                reinterpret_cast<const unsigned long long *>(d_voxel),
-                                                reinterpret_cast<const svo_lights::Light *>(lights), n_lights,
-                                                reinterpret_cast<svo::QueryRay *>(d_rays_out), s);
-    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("light ray launch: ") + hipGetErrorString(e));
-    return SVO_OK;
+    return check_batch_fan(rays, n, hits, voxel, (size_t)n_lights, rays_out, "light rays");
 }
 
 // An object list as svo_set_objects and svo_trace_scene take it (host memory): n_objects in 0 .. 8, and with
@@ -2360,7 +2476,7 @@ int check_object_roots(const svo_ctx *c, const svo_object *objects, int n_object
     return SVO_OK;
 }
 
-// The argument checks of svo_object_rays(_host) that need no device.
+// Its own head: no hit records or voxel keys, and the object before the flags.
 int check_object_ray_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const svo_object *object,
                           const void *rays_out) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
@@ -2369,20 +2485,10 @@ int check_object_ray_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t fla
     if (!object) return fail(SVO_ERR_ARG, "null object");
     if (flags & ~(uint32_t)SVO_QUERY_RAW_DIRECTIONS) return fail(SVO_ERR_ARG, "unknown object-ray flag bits");
     if (int rc = check_object_list(object, 1)) return rc;
-    if (n > MAX_QUERY_RAYS) return fail(SVO_ERR_ARG, "more than 2^31 - 1 rays in one batch");
-    return SVO_OK;
+    return check_batch_count(n, 1, "rays");   // no overlap test: rays_out may be rays
 }
 
-int object_rays_device(const void *d_rays, size_t n, const svo_object *object, void *d_rays_out, hipStream_t s) {
-    svo_objects::Object ob;
-    std::memcpy(&ob, object, sizeof ob);
-    const hipError_t e = svo::launch_object_rays(reinterpret_cast<const svo::QueryRay *>(d_rays), (uint32_t)n, ob,
-                                                 reinterpret_cast<svo::QueryRay *>(d_rays_out), s);
-    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("object ray launch: ") + hipGetErrorString(e));
-    return SVO_OK;
-}
-
-// The argument checks of svo_trace_scene(_host) that need no device: `any_out` = some output was asked for.
+// `any_out` = some output was asked for.
 int check_scene_args(svo_ctx *ctx, const void *rays, size_t n, int stack_mode, uint32_t flags, const svo_object *objects,
                      int n_objects, bool any_out) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
@@ -2393,49 +2499,79 @@ int check_scene_args(svo_ctx *ctx, const void *rays, size_t n, int stack_mode, u
     if (int rc = check_query_args(n, stack_mode, 0u)) return rc;
     if (n_objects > 0 && !objects) return fail(SVO_ERR_ARG, "null object list");
     if (int rc = check_object_list(objects, n_objects)) return rc;
-    return check_object_roots(is_multi(ctx) ? ctx->members[0] : ctx, objects, n_objects);
+    return check_object_roots(batch_context(ctx), objects, n_objects);
 }
 
-// One scene query on context c (single-device), its device selected: arguments checked by the caller.
+// One scene query on context c (single-device), its device selected: arguments and pool checked by the caller.
 int scene_device(svo_ctx *c, const svo_ray *d_rays, size_t n, int stack_mode, uint32_t flags, const svo_object *objects,
                  int n_objects, const svo_query_out &out, int32_t *d_object, hipStream_t s) {
     if ((uintptr_t)d_rays & 15u) return fail(SVO_ERR_ARG, "d_rays must be 16-byte aligned");
-    svo::LaunchParams p;
-    std::memset(&p, 0, sizeof p);
-    p.nodes = c->d_nodes;
-    p.att = c->d_att;
-    p.n_nodes = (uint32_t)std::min<size_t>(c->n_nodes, 0xFFFFFFFFu);
+    svo::LaunchParams p = pool_params(c);
     p.slots = 21;   // every walk of a scene query is guarded, on the full stack (svo_kernel.hip OBJECT_SLOTS)
     p.guard = 1;
-    svo::QueryArgs q;
-    std::memset(&q, 0, sizeof q);
-    q.rays = reinterpret_cast<const svo::QueryRay *>(d_rays);
-    q.n = (uint32_t)n;
-    q.flags = (flags & SVO_QUERY_RAW_DIRECTIONS) ? svo::QUERY_RAW : 0u;
-    q.out.hits = reinterpret_cast<svo::Hit *>(out.hits);
-    q.out.position = reinterpret_cast<float4 *>(out.position);
-    q.out.voxel = reinterpret_cast<unsigned long long *>(out.voxel);
-    q.out.hitmask = reinterpret_cast<unsigned long long *>(out.hitmask);
+    const svo::QueryArgs q = query_args(d_rays, n, flags, out);
     svo_objects::Object obs[svo_objects::MAX_OBJECTS] = {};
     for (int j = 0; j < n_objects; ++j) std::memcpy(obs + j, objects + j, sizeof obs[j]);
-    const hipError_t e = svo::launch_scene_query(p, q, obs, n_objects, !(flags & SVO_SCENE_NO_TERRAIN), d_object, stack_mode, s);
-    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("scene query launch: ") + hipGetErrorString(e));
-    return SVO_OK;
+    return launched(svo::launch_scene_query(p, q, obs, n_objects, !(flags & SVO_SCENE_NO_TERRAIN), d_object, stack_mode, s),
+                    "scene query launch");
 }
 
 int check_sky_args(svo_ctx *ctx, const float *dirs, size_t n, const float *rgba) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
     if (!dirs) return fail(SVO_ERR_ARG, "null direction list");
     if (!rgba) return fail(SVO_ERR_ARG, "null colour output");
-    if (n > 0x7FFFFFFFu) return fail(SVO_ERR_ARG, "more than 2^31 - 1 directions");
+    if (n > MAX_QUERY_RAYS) return fail(SVO_ERR_ARG, "more than 2^31 - 1 directions");
     return SVO_OK;
 }
 
-int sample_sky_device(svo_ctx *c, const void *d_dirs, size_t n, void *d_rgba, hipStream_t s) {
-    const hipError_t e = svo::launch_sample_sky(c->sky, reinterpret_cast<const float4 *>(d_dirs), (uint32_t)n,
-                                                reinterpret_cast<float4 *>(d_rgba), s);
-    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("sky sample launch: ") + hipGetErrorString(e));
-    return SVO_OK;
+int sky_launch(svo_ctx *c, const void *d_dirs, size_t n, void *d_rgba, hipStream_t s) {
+    return launched(svo::launch_sample_sky(c->sky, static_cast<const float4 *>(d_dirs), (uint32_t)n,
+                                           static_cast<float4 *>(d_rgba), s), "sky sample launch");
+}
+
+// The host twin of a call on a traced batch (hits, voxel null where the call has none): the inputs staged,
+// launch(batch, s), and n * fan rays brought back -- fan 0: n rays, written over the staged input.
+template <class F>
+int batch_host(svo_ctx *ctx, const char *name, const void *rays, size_t n, uint32_t flags, const void *hits,
+               const void *voxel, size_t fan, void *rays_out, F &&launch) {
+    return on_device(ctx, name, nullptr, false, [&](svo_ctx *c, hipStream_t s) {
+        HostStage st(c);
+        const size_t out_bytes = 32 * n * std::max<size_t>(fan, 1);
+        const size_t p_rays = st.part(32 * n), p_hits = st.part(hits ? 24 * n : 0), p_vox = st.part(voxel ? 8 * n : 0),
+                     p_out = fan ? st.part(out_bytes) : p_rays;
+        if (int rc = st.begin()) return rc;
+        if (int rc = st.upload(p_rays, rays, 32 * n)) return rc;
+        if (int rc = st.upload(p_hits, hits, 24 * n)) return rc;
+        if (int rc = st.upload(p_vox, voxel, 8 * n)) return rc;
+        if (int rc = launch(batch_of(st.at(p_rays), n, flags, st.at_if(hits, p_hits), st.at_if(voxel, p_vox), st.at(p_out)), s))
+            return rc;
+        if (int rc = st.download(rays_out, p_out, out_bytes)) return rc;
+        return st.finish();
+    });
+}
+
+// The host twin of a trace (svo_trace_rays_lod_host, svo_trace_scene_host): the rays staged, trace(c, d_rays,
+// out, d_object, s) with a part for every output the caller asked for, and those brought back.
+template <class F>
+int traced_host(svo_ctx *ctx, const char *name, const svo_ray *rays, size_t n, svo_hit *hits, float *position,
+                uint64_t *voxel, int32_t *object, F &&trace) {
+    return on_device(ctx, name, nullptr, true, [&](svo_ctx *c, hipStream_t s) {
+        HostStage st(c);
+        const size_t p_rays = st.part(32 * n), p_pos = st.part(16 * n), p_hits = st.part(24 * n), p_vox = st.part(8 * n),
+                     p_id = st.part(object ? 4 * n : 0);
+        if (int rc = st.begin()) return rc;
+        if (int rc = st.upload(p_rays, rays, 32 * n)) return rc;
+        svo_query_out out{};
+        out.hits = st.at_if<svo_hit>(hits, p_hits);
+        out.position = st.at_if<float>(position, p_pos);
+        out.voxel = st.at_if<uint64_t>(voxel, p_vox);
+        if (int rc = trace(c, st.at<const svo_ray>(p_rays), out, st.at_if<int32_t>(object, p_id), s)) return rc;
+        if (int rc = st.download(hits, p_hits, 24 * n)) return rc;
+        if (int rc = st.download(position, p_pos, 16 * n)) return rc;
+        if (int rc = st.download(voxel, p_vox, 8 * n)) return rc;
+        if (int rc = st.download(object, p_id, 4 * n)) return rc;
+        return st.finish();
+    });
 }
 
 }  // namespace
@@ -2449,23 +2585,14 @@ int svo_trace_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n_rays, int stack
 
 int svo_trace_rays_lod(svo_ctx *ctx, const svo_ray *d_rays, size_t n_rays, int stack_mode, uint32_t flags,
                        float ray_size_coef, float ray_size_bias, const svo_query_out *out, void *stream) {
-    if (!ctx) return fail(SVO_ERR_ARG, "null context");
-    if (!lod_pair_ok(ray_size_coef, ray_size_bias)) return fail(SVO_ERR_ARG, LOD_PAIR_MSG);
-    if (!d_rays) return fail(SVO_ERR_ARG, "null ray list");
-    if (!out) return fail(SVO_ERR_ARG, "null svo_query_out");
-    if (!out->hits && !out->position && !out->voxel && !out->hitmask) return fail(SVO_ERR_ARG, "every query output is null");
-    int rc = check_query_args(n_rays, stack_mode, flags);
-    if (rc) return rc;
+    const char *out_error = !out ? "null svo_query_out"
+                            : !out->hits && !out->position && !out->voxel && !out->hitmask ? "every query output is null"
+                                                                                           : nullptr;
+    if (int rc = check_trace_args(ctx, d_rays, n_rays, stack_mode, flags, ray_size_coef, ray_size_bias, out_error)) return rc;
     if (n_rays == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
-        HIP_TRY(hipSetDevice(c->device));
-        return query_device(c, d_rays, n_rays, stack_mode, flags, *out, stream ? (hipStream_t)stream : c->stream,
-                            ray_size_coef, ray_size_bias);
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_trace_rays: ") + e.what());
-    }
+    return on_device(ctx, "svo_trace_rays", stream, true, [&](svo_ctx *c, hipStream_t s) {
+        return query_device(c, d_rays, n_rays, stack_mode, flags, *out, s, ray_size_coef, ray_size_bias);
+    });
 }
 
 int svo_trace_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, int stack_mode, uint32_t flags,
@@ -2473,301 +2600,132 @@ int svo_trace_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, int st
     return svo_trace_rays_lod_host(ctx, rays, n_rays, stack_mode, flags, 0.0f, 0.0f, hits, position, voxel);
 }
 
-int svo_trace_rays_lod_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, int stack_mode, uint32_t flags,
+int svo_trace_rays_lod_host(svo_ctx *ctx, const svo_ray *rays, size_t n, int stack_mode, uint32_t flags,
                             float ray_size_coef, float ray_size_bias, svo_hit *hits, float *position, uint64_t *voxel) {
-    if (!ctx) return fail(SVO_ERR_ARG, "null context");
-    if (!lod_pair_ok(ray_size_coef, ray_size_bias)) return fail(SVO_ERR_ARG, LOD_PAIR_MSG);
-    if (!rays) return fail(SVO_ERR_ARG, "null ray list");
-    if (!hits && !position && !voxel) return fail(SVO_ERR_ARG, "every query output is null");
-    int rc = check_query_args(n_rays, stack_mode, flags);
-    if (rc) return rc;
-    if (n_rays == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
-        HIP_TRY(hipSetDevice(c->device));
-        // staged layout: rays (32 B), positions (16 B), hit records (24 B), voxel keys (8 B) per ray --
-        // every part 16-byte aligned for any n (the records' part starts at a multiple of 48 n)
-        const size_t n = n_rays, off_pos = 32 * n, off_hits = 48 * n, off_vox = (72 * n + 15) & ~(size_t)15;
-        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, off_vox + 8 * n);
-        if (rc) return rc;
-        rc = order_query_scratch(c, c->stream);
-        if (rc) return rc;
-        char *base = static_cast<char *>(c->q_host);
-        // every exit waits for the stream: no copy may still read or write the caller's arrays once
-        // this call has returned (an error included)
-        struct Drain {
-            hipStream_t s;
-            ~Drain() { hipStreamSynchronize(s); }
-        } drain{c->stream};
-        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
-        svo_query_out out{};
-        out.hits = hits ? reinterpret_cast<svo_hit *>(base + off_hits) : nullptr;
-        out.position = position ? reinterpret_cast<float *>(base + off_pos) : nullptr;
-        out.voxel = voxel ? reinterpret_cast<uint64_t *>(base + off_vox) : nullptr;
-        rc = query_device(c, reinterpret_cast<const svo_ray *>(base), n, stack_mode, flags, out, c->stream,
-                          ray_size_coef, ray_size_bias);
-        if (rc) return rc;
-        if (hits) HIP_TRY(hipMemcpyAsync(hits, out.hits, 24 * n, hipMemcpyDeviceToHost, c->stream));
-        if (position) HIP_TRY(hipMemcpyAsync(position, out.position, 16 * n, hipMemcpyDeviceToHost, c->stream));
-        if (voxel) HIP_TRY(hipMemcpyAsync(voxel, out.voxel, 8 * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SVO_OK;
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_trace_rays_host: ") + e.what());
-    }
+    const char *out_error = !hits && !position && !voxel ? "every query output is null" : nullptr;
+    if (int rc = check_trace_args(ctx, rays, n, stack_mode, flags, ray_size_coef, ray_size_bias, out_error)) return rc;
+    if (n == 0) return SVO_OK;
+    return traced_host(ctx, "svo_trace_rays_host", rays, n, hits, position, voxel, nullptr,
+                       [&](svo_ctx *c, const svo_ray *d_rays, const svo_query_out &out, int32_t *, hipStream_t s) {
+                           return query_device(c, d_rays, n, stack_mode, flags, out, s, ray_size_coef, ray_size_bias);
+                       });
 }
 
 int svo_bounce_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
                     const uint64_t *d_voxel, svo_ray *d_rays_out, void *stream) {
-    int rc = check_bounce_args(ctx, d_rays, n, flags, d_hits, d_voxel, d_rays_out);
-    if (rc) return rc;
-    if (((uintptr_t)d_rays | (uintptr_t)d_rays_out) & 15u) return fail(SVO_ERR_ARG, "ray lists must be 16-byte aligned");
-    if (((uintptr_t)d_hits | (uintptr_t)d_voxel) & 7u) return fail(SVO_ERR_ARG, "hit records and voxel keys must be 8-byte aligned");
+    if (int rc = check_bounce_args(ctx, d_rays, n, flags, d_hits, d_voxel, d_rays_out)) return rc;
+    if (int rc = check_batch_alignment(d_rays, d_rays_out, d_hits, d_voxel)) return rc;
     if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        HIP_TRY(hipSetDevice(c->device));
-        return bounce_device(d_rays, n, flags, d_hits, d_voxel, d_rays_out, stream ? (hipStream_t)stream : c->stream);
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_bounce_rays: ") + e.what());
-    }
+    return on_device(ctx, "svo_bounce_rays", stream, false, [&](svo_ctx *, hipStream_t s) {
+        return bounce_launch(batch_of(d_rays, n, flags, d_hits, d_voxel, d_rays_out), s);
+    });
 }
 
 int svo_bounce_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
                          const uint64_t *voxel, svo_ray *rays_out) {
-    int rc = check_bounce_args(ctx, rays, n, flags, hits, voxel, rays_out);
-    if (rc) return rc;
+    if (int rc = check_bounce_args(ctx, rays, n, flags, hits, voxel, rays_out)) return rc;
     if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        HIP_TRY(hipSetDevice(c->device));
-        // staged layout: rays (32 B, bounced in place), hit records (24 B), voxel keys (8 B) per ray
-        const size_t off_hits = 32 * n, off_vox = 56 * n;
-        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, 64 * n);
-        if (rc) return rc;
-        rc = order_query_scratch(c, c->stream);
-        if (rc) return rc;
-        char *base = static_cast<char *>(c->q_host);
-        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
-            hipStream_t s;
-            ~Drain() { hipStreamSynchronize(s); }
-        } drain{c->stream};
-        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + off_hits, hits, 24 * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + off_vox, voxel, 8 * n, hipMemcpyHostToDevice, c->stream));
-        rc = bounce_device(base, n, flags, base + off_hits, base + off_vox, base, c->stream);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(rays_out, base, 32 * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SVO_OK;
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_bounce_rays_host: ") + e.what());
-    }
+    return batch_host(ctx, "svo_bounce_rays_host", rays, n, flags, hits, voxel, 0, rays_out, bounce_launch);   // in place
 }
 
 int svo_ambient_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
                      const uint64_t *d_voxel, int n_rays, float radius, uint32_t variant, svo_ray *d_rays_out,
                      void *stream) {
-    int rc = check_ambient_args(ctx, d_rays, n, flags, d_hits, d_voxel, n_rays, radius, variant, d_rays_out);
-    if (rc) return rc;
-    if (((uintptr_t)d_rays | (uintptr_t)d_rays_out) & 15u) return fail(SVO_ERR_ARG, "ray lists must be 16-byte aligned");
-    if (((uintptr_t)d_hits | (uintptr_t)d_voxel) & 7u) return fail(SVO_ERR_ARG, "hit records and voxel keys must be 8-byte aligned");
+    if (int rc = check_ambient_args(ctx, d_rays, n, flags, d_hits, d_voxel, n_rays, radius, variant, d_rays_out)) return rc;
+    if (int rc = check_batch_alignment(d_rays, d_rays_out, d_hits, d_voxel)) return rc;
     if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        HIP_TRY(hipSetDevice(c->device));
-        return ambient_device(d_rays, n, flags, d_hits, d_voxel, n_rays, radius, variant, d_rays_out,
-                              stream ? (hipStream_t)stream : c->stream);
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_ambient_rays: ") + e.what());
-    }
+    return on_device(ctx, "svo_ambient_rays", stream, false, [&](svo_ctx *, hipStream_t s) {
+        return ambient_launch(batch_of(d_rays, n, flags, d_hits, d_voxel, d_rays_out), n_rays, radius, variant, s);
+    });
 }
 
 int svo_ambient_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
                           const uint64_t *voxel, int n_rays, float radius, uint32_t variant, svo_ray *rays_out) {
-    int rc = check_ambient_args(ctx, rays, n, flags, hits, voxel, n_rays, radius, variant, rays_out);
-    if (rc) return rc;
+    if (int rc = check_ambient_args(ctx, rays, n, flags, hits, voxel, n_rays, radius, variant, rays_out)) return rc;
     if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        HIP_TRY(hipSetDevice(c->device));
-        // staged layout: rays (32 B), hit records (24 B), voxel keys (8 B) per input, then the output rays
-        const size_t off_hits = 32 * n, off_vox = 56 * n, off_out = 64 * n, out_bytes = 32 * n * (size_t)n_rays;
-        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, off_out + out_bytes);
-        if (rc) return rc;
-        rc = order_query_scratch(c, c->stream);
-        if (rc) return rc;
-        char *base = static_cast<char *>(c->q_host);
-        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
-            hipStream_t s;
-            ~Drain() { hipStreamSynchronize(s); }
-        } drain{c->stream};
-        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + off_hits, hits, 24 * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + off_vox, voxel, 8 * n, hipMemcpyHostToDevice, c->stream));
-        rc = ambient_device(base, n, flags, base + off_hits, base + off_vox, n_rays, radius, variant, base + off_out,
-                            c->stream);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(rays_out, base + off_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SVO_OK;
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_ambient_rays_host: ") + e.what());
-    }
+    return batch_host(ctx, "svo_ambient_rays_host", rays, n, flags, hits, voxel, (size_t)n_rays, rays_out,
+                      [&](const Batch &b, hipStream_t s) { return ambient_launch(b, n_rays, radius, variant, s); });
 }
 
 int svo_light_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
                    const uint64_t *d_voxel, const svo_light *lights, int n_lights, svo_ray *d_rays_out, void *stream) {
-    int rc = check_light_args(ctx, d_rays, n, flags, d_hits, d_voxel, lights, n_lights, d_rays_out);
-    if (rc) return rc;
-    if (((uintptr_t)d_rays | (uintptr_t)d_rays_out) & 15u) return fail(SVO_ERR_ARG, "ray lists must be 16-byte aligned");
-    if (((uintptr_t)d_hits | (uintptr_t)d_voxel) & 7u) return fail(SVO_ERR_ARG, "hit records and voxel keys must be 8-byte aligned");
+    if (int rc = check_light_args(ctx, d_rays, n, flags, d_hits, d_voxel, lights, n_lights, d_rays_out)) return rc;
+    if (int rc = check_batch_alignment(d_rays, d_rays_out, d_hits, d_voxel)) return rc;
     if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        HIP_TRY(hipSetDevice(c->device));
-        return light_device(d_rays, n, flags, d_hits, d_voxel, lights, n_lights, d_rays_out,
-                            stream ? (hipStream_t)stream : c->stream);
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_light_rays: ") + e.what());
-    }
+    return on_device(ctx, "svo_light_rays", stream, false, [&](svo_ctx *, hipStream_t s) {
+        return light_launch(batch_of(d_rays, n, flags, d_hits, d_voxel, d_rays_out), lights, n_lights, s);
+    });
 }
 
 int svo_light_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
                         const uint64_t *voxel, const svo_light *lights, int n_lights, svo_ray *rays_out) {
-    int rc = check_light_args(ctx, rays, n, flags, hits, voxel, lights, n_lights, rays_out);
-    if (rc) return rc;
+    if (int rc = check_light_args(ctx, rays, n, flags, hits, voxel, lights, n_lights, rays_out)) return rc;
     if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        HIP_TRY(hipSetDevice(c->device));
-        // staged layout: rays (32 B), hit records (24 B), voxel keys (8 B) per input, then the output rays
-        const size_t off_hits = 32 * n, off_vox = 56 * n, off_out = 64 * n, out_bytes = 32 * n * (size_t)n_lights;
-        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, off_out + out_bytes);
-        if (rc) return rc;
-        rc = order_query_scratch(c, c->stream);
-        if (rc) return rc;
-        char *base = static_cast<char *>(c->q_host);
-        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
-            hipStream_t s;
-            ~Drain() { hipStreamSynchronize(s); }
-        } drain{c->stream};
-        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + off_hits, hits, 24 * n, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(base + off_vox, voxel, 8 * n, hipMemcpyHostToDevice, c->stream));
-        rc = light_device(base, n, flags, base + off_hits, base + off_vox, lights, n_lights, base + off_out, c->stream);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(rays_out, base + off_out, out_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SVO_OK;
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_light_rays_host: ") + e.what());
-    }
+    return batch_host(ctx, "svo_light_rays_host", rays, n, flags, hits, voxel, (size_t)n_lights, rays_out,
+                      [&](const Batch &b, hipStream_t s) { return light_launch(b, lights, n_lights, s); });
 }
 
 int svo_object_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_object *object,
                     svo_ray *d_rays_out, void *stream) {
-    int rc = check_object_ray_args(ctx, d_rays, n, flags, object, d_rays_out);
-    if (rc) return rc;
-    if (((uintptr_t)d_rays | (uintptr_t)d_rays_out) & 15u) return fail(SVO_ERR_ARG, "ray lists must be 16-byte aligned");
+    if (int rc = check_object_ray_args(ctx, d_rays, n, flags, object, d_rays_out)) return rc;
+    if (int rc = check_batch_alignment(d_rays, d_rays_out, nullptr, nullptr)) return rc;
     if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        HIP_TRY(hipSetDevice(c->device));
-        return object_rays_device(d_rays, n, object, d_rays_out, stream ? (hipStream_t)stream : c->stream);
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_object_rays: ") + e.what());
-    }
+    return on_device(ctx, "svo_object_rays", stream, false, [&](svo_ctx *, hipStream_t s) {
+        return object_rays_launch(batch_of(d_rays, n, flags, nullptr, nullptr, d_rays_out), object, s);
+    });
 }
 
 int svo_object_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_object *object,
                          svo_ray *rays_out) {
-    int rc = check_object_ray_args(ctx, rays, n, flags, object, rays_out);
-    if (rc) return rc;
+    if (int rc = check_object_ray_args(ctx, rays, n, flags, object, rays_out)) return rc;
     if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        HIP_TRY(hipSetDevice(c->device));
-        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, 32 * n);
-        if (rc) return rc;
-        rc = order_query_scratch(c, c->stream);
-        if (rc) return rc;
-        char *base = static_cast<char *>(c->q_host);
-        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
-            hipStream_t s;
-            ~Drain() { hipStreamSynchronize(s); }
-        } drain{c->stream};
-        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
-        rc = object_rays_device(base, n, object, base, c->stream);   // in place
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(rays_out, base, 32 * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SVO_OK;
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_object_rays_host: ") + e.what());
-    }
+    return batch_host(ctx, "svo_object_rays_host", rays, n, flags, nullptr, nullptr, 0, rays_out,   // in place
+                      [&](const Batch &b, hipStream_t s) { return object_rays_launch(b, object, s); });
 }
 
 int svo_trace_scene(svo_ctx *ctx, const svo_ray *d_rays, size_t n, int stack_mode, uint32_t flags,
                     const svo_object *objects, int n_objects, const svo_query_out *out, int32_t *d_object, void *stream) {
     const bool any_out = d_object || (out && (out->hits || out->position || out->voxel || out->hitmask));
-    int rc = check_scene_args(ctx, d_rays, n, stack_mode, flags, objects, n_objects, any_out);
-    if (rc) return rc;
+    if (int rc = check_scene_args(ctx, d_rays, n, stack_mode, flags, objects, n_objects, any_out)) return rc;
     if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
-        HIP_TRY(hipSetDevice(c->device));
+    return on_device(ctx, "svo_trace_scene", stream, true, [&](svo_ctx *c, hipStream_t s) {
         const svo_query_out none{};
-        return scene_device(c, d_rays, n, stack_mode, flags, objects, n_objects, out ? *out : none, d_object,
-                            stream ? (hipStream_t)stream : c->stream);
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_trace_scene: ") + e.what());
-    }
+        return scene_device(c, d_rays, n, stack_mode, flags, objects, n_objects, out ? *out : none, d_object, s);
+    });
 }
 
 int svo_trace_scene_host(svo_ctx *ctx, const svo_ray *rays, size_t n, int stack_mode, uint32_t flags,
                          const svo_object *objects, int n_objects, svo_hit *hits, float *position, uint64_t *voxel,
                          int32_t *object) {
-    int rc = check_scene_args(ctx, rays, n, stack_mode, flags, objects, n_objects, hits || position || voxel || object);
-    if (rc) return rc;
+    if (int rc = check_scene_args(ctx, rays, n, stack_mode, flags, objects, n_objects, hits || position || voxel || object))
+        return rc;
     if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        if (c->n_nodes == 0) return fail(SVO_ERR_STATE, "no node pool uploaded (svo_set_buffer)");
-        HIP_TRY(hipSetDevice(c->device));
-        // staged layout: rays (32 B), positions (16 B), hit records (24 B), voxel keys (8 B), ids (4 B) per ray;
-        // every part 16-byte aligned for any n
-        const size_t off_pos = 32 * n, off_hits = 48 * n, off_vox = (72 * n + 15) & ~(size_t)15,
-                     off_id = (off_vox + 8 * n + 15) & ~(size_t)15;
-        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, off_id + 4 * n);
-        if (rc) return rc;
-        rc = order_query_scratch(c, c->stream);
-        if (rc) return rc;
-        char *base = static_cast<char *>(c->q_host);
-        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
-            hipStream_t s;
-            ~Drain() { hipStreamSynchronize(s); }
-        } drain{c->stream};
-        HIP_TRY(hipMemcpyAsync(base, rays, 32 * n, hipMemcpyHostToDevice, c->stream));
-        svo_query_out out{};
-        out.hits = hits ? reinterpret_cast<svo_hit *>(base + off_hits) : nullptr;
-        out.position = position ? reinterpret_cast<float *>(base + off_pos) : nullptr;
-        out.voxel = voxel ? reinterpret_cast<uint64_t *>(base + off_vox) : nullptr;
-        int32_t *d_object = object ? reinterpret_cast<int32_t *>(base + off_id) : nullptr;
-        rc = scene_device(c, reinterpret_cast<const svo_ray *>(base), n, stack_mode, flags, objects, n_objects, out,
-                          d_object, c->stream);
-        if (rc) return rc;
-        if (hits) HIP_TRY(hipMemcpyAsync(hits, out.hits, 24 * n, hipMemcpyDeviceToHost, c->stream));
-        if (position) HIP_TRY(hipMemcpyAsync(position, out.position, 16 * n, hipMemcpyDeviceToHost, c->stream));
-        if (voxel) HIP_TRY(hipMemcpyAsync(voxel, out.voxel, 8 * n, hipMemcpyDeviceToHost, c->stream));
-        if (object) HIP_TRY(hipMemcpyAsync(object, d_object, 4 * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SVO_OK;
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_trace_scene_host: ") + e.what());
-    }
+    return traced_host(ctx, "svo_trace_scene_host", rays, n, hits, position, voxel, object,
+                       [&](svo_ctx *c, const svo_ray *d_rays, const svo_query_out &out, int32_t *d_object, hipStream_t s) {
+                           return scene_device(c, d_rays, n, stack_mode, flags, objects, n_objects, out, d_object, s);
+                       });
+}
+
+int svo_sample_sky(svo_ctx *ctx, const float *d_dirs, size_t n, float *d_rgba, void *stream) {
+    if (int rc = check_sky_args(ctx, d_dirs, n, d_rgba)) return rc;
+    if (((uintptr_t)d_dirs | (uintptr_t)d_rgba) & 15u) return fail(SVO_ERR_ARG, "directions and colours must be 16-byte aligned");
+    if (n == 0) return SVO_OK;
+    return on_device(ctx, "svo_sample_sky", stream, false,
+                     [&](svo_ctx *c, hipStream_t s) { return sky_launch(c, d_dirs, n, d_rgba, s); });
+}
+
+int svo_sample_sky_host(svo_ctx *ctx, const float *dirs, size_t n, float *rgba) {
+    if (int rc = check_sky_args(ctx, dirs, n, rgba)) return rc;
+    if (n == 0) return SVO_OK;
+    return on_device(ctx, "svo_sample_sky_host", nullptr, false, [&](svo_ctx *c, hipStream_t s) {
+        HostStage st(c);
+        const size_t p_dirs = st.part(16 * n);   // the directions, 16 bytes each, sampled in place
+        if (int rc = st.begin()) return rc;
+        if (int rc = st.upload(p_dirs, dirs, 16 * n)) return rc;
+        if (int rc = sky_launch(c, st.at(p_dirs), n, st.at(p_dirs), s)) return rc;
+        if (int rc = st.download(rgba, p_dirs, 16 * n)) return rc;
+        return st.finish();
+    });
 }
 
 int svo_get_config(svo_ctx *ctx, svo_config *cfg) {
@@ -3206,48 +3164,6 @@ int svo_get_skybox(svo_ctx *ctx, int *width, int *height, uint32_t *flags) {
     if (height) *height = ctx->sky.height;
     if (flags) *flags = ctx->sky.flags;
     return SVO_OK;
-}
-
-int svo_sample_sky(svo_ctx *ctx, const float *d_dirs, size_t n, float *d_rgba, void *stream) {
-    int rc = check_sky_args(ctx, d_dirs, n, d_rgba);
-    if (rc) return rc;
-    if (((uintptr_t)d_dirs | (uintptr_t)d_rgba) & 15u) return fail(SVO_ERR_ARG, "directions and colours must be 16-byte aligned");
-    if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        HIP_TRY(hipSetDevice(c->device));
-        return sample_sky_device(c, d_dirs, n, d_rgba, stream ? (hipStream_t)stream : c->stream);
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_sample_sky: ") + e.what());
-    }
-}
-
-int svo_sample_sky_host(svo_ctx *ctx, const float *dirs, size_t n, float *rgba) {
-    int rc = check_sky_args(ctx, dirs, n, rgba);
-    if (rc) return rc;
-    if (n == 0) return SVO_OK;
-    try {
-        svo_ctx *c = is_multi(ctx) ? ctx->members[0] : ctx;
-        HIP_TRY(hipSetDevice(c->device));
-        // staged in the ray queries' scratch: the directions, 16 bytes each, sampled in place
-        rc = grow_query_scratch(&c->q_host, &c->q_host_cap, 16 * n);
-        if (rc) return rc;
-        rc = order_query_scratch(c, c->stream);
-        if (rc) return rc;
-        char *base = static_cast<char *>(c->q_host);
-        struct Drain {   // no copy may still touch the caller's arrays once this call has returned
-            hipStream_t s;
-            ~Drain() { hipStreamSynchronize(s); }
-        } drain{c->stream};
-        HIP_TRY(hipMemcpyAsync(base, dirs, 16 * n, hipMemcpyHostToDevice, c->stream));
-        rc = sample_sky_device(c, base, n, base, c->stream);
-        if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(rgba, base, 16 * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        return SVO_OK;
-    } catch (const std::exception &e) {
-        return fail(SVO_ERR_HIP, std::string("svo_sample_sky_host: ") + e.what());
-    }
 }
 
 int svo_get_lod(svo_ctx *ctx, float *ray_size_coef, float *ray_size_bias) {

@@ -19,8 +19,8 @@ rounding, only + - * /, sqrt, compares and selects:
 """
 import numpy as np
 
-from ._lib import HIT_DTYPE, LIGHT_DTYPE, LIGHT_NO_SHADOW, MAX_LIGHTS, RAY_DTYPE
-from .query import sanitize_rays
+from ._lib import LIGHT_DTYPE, LIGHT_NO_SHADOW, MAX_LIGHTS
+from .query import batch_arrays, sanitize_rays
 from .reflection import dead_rays, entry_face
 
 MAX_COORD = 2.0 ** 20
@@ -57,11 +57,7 @@ def make_lights(lights):
 def _geometry(rays, hits, voxel, lights, raw):
     """Steps 1-3 for every (record, light) pair: hit [n], Q [n, 3], L [n, m, 3], d2, u, facing, in_range [n, m]."""
     f = np.float32
-    rays = np.ascontiguousarray(rays, RAY_DTYPE).reshape(-1)
-    hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
-    voxel = np.ascontiguousarray(voxel, np.uint64).reshape(-1)
-    if not len(rays) == len(hits) == len(voxel):
-        raise ValueError(f"{len(rays)} rays, {len(hits)} hit records, {len(voxel)} voxel keys")
+    rays, hits, voxel = batch_arrays(rays, hits, voxel)
     lights = make_lights(lights)
     n = len(rays)
     rows = np.arange(n)

@@ -13,7 +13,7 @@ knows exactly which rays were traced and with which directions:
 """
 import numpy as np
 
-from ._lib import RAY_DTYPE
+from ._lib import HIT_DTYPE, RAY_DTYPE
 
 DIR_EPSILON = np.float32(2.0 ** -23)   # exp2(-s_max), NVIDIASVO.compute:2-3
 
@@ -31,6 +31,17 @@ def make_rays(origins, dirs, t_max=np.inf):
     rays["dir"] = dirs
     rays["t_max"] = np.broadcast_to(np.asarray(t_max, np.float32), (len(rays),))
     return rays
+
+
+def batch_arrays(rays, hits, voxel):
+    """A traced batch as the bounce, ambient and light-ray calls take it: (rays, hits, voxel) contiguous and
+    flat, RAY_DTYPE, HIT_DTYPE and uint64, one hit record and one voxel key per ray."""
+    rays = np.ascontiguousarray(rays, RAY_DTYPE).reshape(-1)
+    hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
+    voxel = np.ascontiguousarray(voxel, np.uint64).reshape(-1)
+    if not len(rays) == len(hits) == len(voxel):
+        raise ValueError(f"{len(rays)} rays, {len(hits)} hit records, {len(voxel)} voxel keys")
+    return rays, hits, voxel
 
 
 def sanitize_rays(rays, raw=False):

@@ -31,6 +31,7 @@ import numpy as np
 from . import _lib
 from ._lib import HIT_DTYPE, LAYOUT_BAND, LAYOUT_FRAME, STACK_EXACT, STACK_HLSL, SvoError, SvoFrame, check, make_band
 from .camera import column_major, main_camera, main_light
+from .query import batch_arrays
 from .svo_data import SVOData
 
 # RaytracingMaster.cs:113-115: "one gibibyte of memory" / 8 elements of 4 bytes
@@ -548,11 +549,7 @@ class RaytracingMaster:
         numpy statement): rays (svo_ray records), their hit records and voxel keys as TraceRays
         returned them; raw: whether the batch was traced with raw=True.  Returns the bounce rays
         (RAY_DTYPE [n]): a dead ray (zero direction, invalid to TraceRays) where there was no hit."""
-        rays = np.ascontiguousarray(rays, _lib.RAY_DTYPE).reshape(-1)
-        hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
-        voxel = np.ascontiguousarray(voxel, np.uint64).reshape(-1)
-        if not len(rays) == len(hits) == len(voxel):
-            raise ValueError(f"{len(rays)} rays, {len(hits)} hit records, {len(voxel)} voxel keys")
+        rays, hits, voxel = batch_arrays(rays, hits, voxel)
         out = np.zeros(len(rays), _lib.RAY_DTYPE)
         check(_lib.lib().svo_bounce_rays_host(self._ctx, rays.ctypes.data, len(rays), self._query_flags(False, raw),
                                               hits.ctypes.data, voxel.ctypes.data, out.ctypes.data),
@@ -571,11 +568,7 @@ class RaytracingMaster:
         statement): rays, their hit records and voxel keys as TraceRays returned them; raw: whether the
         batch was traced with raw=True.  Returns RAY_DTYPE [n * n_rays], entry i * n_rays + k = ray k of
         rays[i]: dead rays (zero direction, invalid to TraceRays) where there was no hit."""
-        rays = np.ascontiguousarray(rays, _lib.RAY_DTYPE).reshape(-1)
-        hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
-        voxel = np.ascontiguousarray(voxel, np.uint64).reshape(-1)
-        if not len(rays) == len(hits) == len(voxel):
-            raise ValueError(f"{len(rays)} rays, {len(hits)} hit records, {len(voxel)} voxel keys")
+        rays, hits, voxel = batch_arrays(rays, hits, voxel)
         out = np.zeros(len(rays) * max(int(n_rays), 0), _lib.RAY_DTYPE)
         check(_lib.lib().svo_ambient_rays_host(self._ctx, rays.ctypes.data, len(rays), self._query_flags(False, raw),
                                                hits.ctypes.data, voxel.ctypes.data, int(n_rays), float(radius),
@@ -597,11 +590,7 @@ class RaytracingMaster:
         rays[i] toward lights[j] with t_max 1 (the light itself): a dead ray where there was no hit, or the
         light lies behind the entry face or out of range."""
         from .lights import make_lights
-        rays = np.ascontiguousarray(rays, _lib.RAY_DTYPE).reshape(-1)
-        hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
-        voxel = np.ascontiguousarray(voxel, np.uint64).reshape(-1)
-        if not len(rays) == len(hits) == len(voxel):
-            raise ValueError(f"{len(rays)} rays, {len(hits)} hit records, {len(voxel)} voxel keys")
+        rays, hits, voxel = batch_arrays(rays, hits, voxel)
         rec = make_lights(lights)
         out = np.zeros(len(rays) * len(rec), _lib.RAY_DTYPE)
         check(_lib.lib().svo_light_rays_host(self._ctx, rays.ctypes.data, len(rays), self._query_flags(False, raw),

@@ -20,8 +20,8 @@ inside the voxel just hit.  Here the ray leaves through the cube face it entered
 """
 import numpy as np
 
-from ._lib import HIT_DTYPE, RAY_DTYPE
-from .query import sanitize_rays
+from ._lib import RAY_DTYPE
+from .query import batch_arrays, sanitize_rays
 
 
 def dead_rays(n):
@@ -60,11 +60,7 @@ def bounce_rays(rays, hits, voxel, raw=False):
     (HIT_DTYPE) has flag bit 0, else the dead ray.  voxel: the hits' voxel keys (uint64).
     raw: rays were traced with SVO_QUERY_RAW_DIRECTIONS (no small-direction clamp)."""
     f = np.float32
-    rays = np.ascontiguousarray(rays, RAY_DTYPE).reshape(-1)
-    hits = np.ascontiguousarray(hits, HIT_DTYPE).reshape(-1)
-    voxel = np.ascontiguousarray(voxel, np.uint64).reshape(-1)
-    if not len(rays) == len(hits) == len(voxel):
-        raise ValueError(f"{len(rays)} rays, {len(hits)} hit records, {len(voxel)} voxel keys")
+    rays, hits, voxel = batch_arrays(rays, hits, voxel)
     traced, _ = sanitize_rays(rays, raw=raw)
     o, d = traced["origin"], traced["dir"]
     n = np.stack([hits["nx"], hits["ny"], hits["nz"]], axis=1)
