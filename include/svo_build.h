@@ -104,6 +104,75 @@ int svob_build_sampler_ex(int device, int sampler, int max_level, const svob_lim
 int svob_surface_leaves_ex(int device, int sampler, int max_level, const svob_limits *limits,
                            svob_report *report, size_t *n_leaves, uint64_t **morton_out, float **normals_out);
 
+/*
+ * Triangle meshes.  svob_build_mesh voxelises an indexed triangle mesh into surface leaves on
+ * HIP device `device` and lays them out as svob_build_from_leaves does; svob_mesh_leaves returns
+ * the leaves alone.  Vertex positions are in the cube's own unit frame [0,1]^3 (the tracer's
+ * [1,2]^3); with n = 2^(max_level-1) the grid coordinate is p * n and voxel (i,j,k) is the
+ * closed box [i,i+1] x [j,j+1] x [k,k+1].
+ *   occupancy  a voxel is a surface leaf iff the closed triangle overlaps the closed box, decided
+ *              by one f32 rule (the two-sided Schwarz-Seidel triangle/box test: three box
+ *              intervals, the plane against the box's critical corner, three edge functions in
+ *              each of the xy, yz and zx projections), stated term for term in
+ *              raytracingtest_amd/csrc/svo_voxelize.h and in numpy in raytracingtest_amd/voxelize.py.
+ *              It errs by at most 10 u (E + 2)(1 + kappa) voxel, u = 2^-24, E the triangle's
+ *              largest extent in voxels, kappa the cancellation of its normal (the header derives it).
+ *   skipped    a triangle whose normal normalises to zero (Vector3.Normalize, magnitude <= 1e-5
+ *              in grid units) is skipped and counted in `degenerate`; one whose bounding box
+ *              misses the cube in `outside`.  Parts outside [0,1]^3 contribute no voxels.
+ *   owner      of the triangles that overlap a voxel the lowest index owns it.
+ *   normal     Normalize((v1 - v0) x (v2 - v0)) of the owner: counter-clockwise front faces give
+ *              outward normals, as the samplers' are; SVOB_MESH_FLIP_WINDING negates it.
+ *   colour     with `colors`: the owner's three vertex colours at the barycentric coordinates of
+ *              the voxel centre projected onto the owner's plane, each clamped at 0 and
+ *              renormalised to sum 1.  Without: position - 1 (NaiveCreator.cs:66), as
+ *              svob_build_from_leaves with colors = NULL.
+ * The result depends on nothing else: not on svob_limits, the launch geometry or the order in
+ * which the device meets the triangles.
+ *
+ * Refused with SVOB -1 before any launch: a NULL mesh, a size below the two header words or above
+ * this library's (svob_mesh is versioned by size like svob_limits; fields past the caller's size
+ * are zero), unknown flag bits, n_triangles >= 2^32 - 1, a non-finite position, an index >=
+ * n_vertices, max_level outside [2, 22], and a grid of which svob_limits.cell_bytes does not hold
+ * one plane (max_level >= 15 at the default 512 MiB).
+ *
+ * Slab rule for the mesh pass: the owner grid holds one uint32 per voxel and needs no halo, so a
+ * z-slab of `rows` planes takes 4 n^2 rows bytes:
+ *     rows = clamp(cell_bytes / (4 n^2), 1, n)          (slab_rows == 0)
+ *     rows = clamp(slab_rows, 1, n)                     (slab_rows  > 0)
+ * One slab up to max_level 10, 128 planes at max_level 11, 2 at max_level 14.  list_capacity,
+ * max_blocks and svob_report keep their meaning: `relaunches` counts compactions repeated because
+ * a slab held more leaves than the list, `normals_regrown` the re-allocation for the attribute pass.
+ */
+enum { SVOB_MESH_FLIP_WINDING = 1 };
+typedef struct svob_mesh {          /* versioned by size like svob_limits */
+    uint32_t size, flags;
+    const float    *positions;  size_t n_vertices;   /* xyz, cube frame [0,1]^3 */
+    const uint32_t *indices;    size_t n_triangles;  /* 3 per triangle */
+    const float    *colors;                          /* rgb per vertex in [0,1], or NULL */
+} svob_mesh;
+typedef struct svob_mesh_stats {    /* caller sets size; at most size bytes written */
+    uint32_t size, reserved;
+    uint64_t degenerate, outside, candidates, overlaps;   /* triangles, triangles, tests run, (voxel, triangle) hits */
+} svob_mesh_stats;
+
+/* Mesh -> pool.  limits, report, stats may be NULL.  out: freed with svob_free. */
+int svob_build_mesh (int device, const svob_mesh *mesh, int max_level, const svob_limits *limits,
+                     svob_report *report, svob_mesh_stats *stats, svob_result *out);
+/* Mesh -> surface leaves, Morton-sorted unique codes (x bit 0, y bit 1, z bit 2), normals (float3),
+ * colours (float3; colors_out may be NULL and receives NULL when the mesh has no colours) and the
+ * owning triangle of each leaf; malloc'd, freed with svob_free_ptr. */
+int svob_mesh_leaves(int device, const svob_mesh *mesh, int max_level, const svob_limits *limits,
+                     svob_report *report, svob_mesh_stats *stats, size_t *n_leaves,
+                     uint64_t **morton_out, float **normals_out, float **colors_out, uint32_t **owner_out);
+
+/* Measurement (tools/voxelize_bench.py): with enable != 0 the calling thread's later mesh calls time
+ * every kernel with device events and wait after each launch -- slower builds, same results.
+ * ms_out (NULL-able) first receives the sums of the thread's last timed call, in milliseconds:
+ * setup, count, scan, overlap, compact, attributes. */
+enum { SVOB_MESH_KERNELS = 6 };
+int svob_mesh_profile(int enable, double *ms_out /* SVOB_MESH_KERNELS */);
+
 /* Evaluate a sampler on the host (for tests): n points (x,y,z interleaved). */
 int svob_eval_sampler(int sampler, size_t n, const float *xyz, float *out);
 

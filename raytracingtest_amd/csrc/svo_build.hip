@@ -29,6 +29,8 @@
 //                  re-allocates when all leaves exceed the capacity.
 //   max_blocks     cap on each launch's blocks, 65,536; the kernels' stride loops cover the rest.
 // None of them changes a result.  svob_report says which of these paths a call took.
+// The mesh pass (svob_build_mesh, "meshes" below) reads the same fields for its owner grid of 4-byte
+// cells without a halo: rows = clamp(cell_bytes / (4 n^2), 1, n), and a budget below one plane is refused.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -40,6 +42,7 @@
 #include <vector>
 
 #include "svo_build.h"
+#include "svo_voxelize.h"
 
 namespace {
 
@@ -768,6 +771,505 @@ int surface_leaves_gpu(int device, int type, int max_level, const Limits &lim, s
     return SVOB_OK;
 }
 
+// ------------------------------------------------------------------ meshes
+// svob_build_mesh / svob_mesh_leaves: triangles -> surface leaves by the rule of svo_voxelize.h.
+//   mesh_setup_kernel    once per build, one lane per triangle: the rule's constants, the clipped box, the flags.
+//   per z-slab of `rows` planes (an owner grid of rows x n x n uint32, all NO_OWNER):
+//     mesh_count_kernel    candidates of every triangle's box in the slab; an exclusive scan over them
+//     mesh_overlap_kernel  one lane per CANDIDATE VOXEL: candidate g belongs to the triangle t with
+//                          scan[t] <= g < scan[t + 1], found by a search over the whole scan for the wave's first
+//                          and last candidate (wave-uniform) and refined per lane between the two; the rule, and
+//                          atomicMin(cell, t) on a hit.  At most MESH_LAUNCH_CANDIDATES per launch.
+//     mesh_compact_kernel  occupied cells -> (morton, owner) through classify_kernel's counter / capacity protocol
+//   host: sort by code (codes are unique); mesh_attr_kernel: normal and colour of every sorted leaf from its owner.
+using svo_voxelize::Tri;
+constexpr uint64_t MESH_LAUNCH_CANDIDATES = 1ull << 28;
+
+struct Mesh {   // svob_mesh after read_mesh
+    uint32_t flags = 0;
+    const float *positions = nullptr;
+    size_t n_vertices = 0;
+    const uint32_t *indices = nullptr;
+    size_t n_triangles = 0;
+    const float *colors = nullptr;
+};
+
+__device__ inline unsigned long long wave_sum(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;   // lane 0 holds the sum
+}
+
+__global__ void mesh_setup_kernel(const float *__restrict__ pos, const uint32_t *__restrict__ idx, uint32_t n_tri, int n,
+                                  Tri *__restrict__ tris, unsigned long long *__restrict__ stats) {
+    unsigned long long degenerate = 0, outside = 0, cand = 0;
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t < n_tri; t += (size_t)gridDim.x * blockDim.x) {
+        float p[9];
+        for (int k = 0; k < 3; ++k) {
+            const size_t v = idx[3 * t + k];
+            p[3 * k] = pos[3 * v];
+            p[3 * k + 1] = pos[3 * v + 1];
+            p[3 * k + 2] = pos[3 * v + 2];
+        }
+        Tri *tri = &tris[t];
+        svo_voxelize::setup(p, n, tri);
+        const uint32_t f = tri->flags;
+        if (f & svo_voxelize::TRI_DEGENERATE) ++degenerate;
+        else if (f & svo_voxelize::TRI_OUTSIDE) ++outside;
+        cand += svo_voxelize::candidates(*tri, 0, n - 1);
+    }
+    degenerate = wave_sum(degenerate);
+    outside = wave_sum(outside);
+    cand = wave_sum(cand);
+    if ((threadIdx.x & 63u) == 0) {
+        if (degenerate) atomicAdd(&stats[0], degenerate);
+        if (outside) atomicAdd(&stats[1], outside);
+        if (cand) atomicAdd(&stats[2], cand);
+    }
+}
+
+// counts[t] = candidates of triangle t in planes [z0, z1]; counts[n_tri] = 0 (the scan's total lands there)
+__global__ void mesh_count_kernel(const Tri *__restrict__ tris, uint32_t n_tri, int z0, int z1,
+                                  unsigned long long *__restrict__ counts) {
+    for (size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x; t <= n_tri; t += (size_t)gridDim.x * blockDim.x)
+        counts[t] = t < n_tri ? svo_voxelize::candidates(tris[t], z0, z1) : 0ull;
+}
+
+// Exclusive scan of counts[0 .. len) in place by ONE block of 256 threads: tiles of 256 with a running carry.
+// len = triangles + 1; 1,281 tiles for the 327,680 triangles of a seven-fold icosphere.
+constexpr int MESH_SCAN_ITEMS = 8;   // consecutive items per thread: tiles of 2,048
+__global__ void __launch_bounds__(256) mesh_scan_kernel(unsigned long long *__restrict__ counts, size_t len) {
+    __shared__ unsigned long long wave_total[4];
+    __shared__ unsigned long long carry_s;
+    const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) carry_s = 0;
+    __syncthreads();
+    for (size_t base = 0; base < len; base += 256 * MESH_SCAN_ITEMS) {
+        const size_t i0 = base + (size_t)threadIdx.x * MESH_SCAN_ITEMS;
+        unsigned long long item[MESH_SCAN_ITEMS];
+        unsigned long long own = 0;   // the thread's items, then the exclusive scan inside the thread
+        for (int k = 0; k < MESH_SCAN_ITEMS; ++k) {
+            const unsigned long long c = i0 + k < len ? counts[i0 + k] : 0ull;
+            item[k] = own;
+            own += c;
+        }
+        unsigned long long v = own;   // inclusive scan of the threads' sums inside the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long up = __shfl_up(v, o, 64);
+            if (lane >= (unsigned)o) v += up;
+        }
+        if (lane == 63) wave_total[wave] = v;
+        __syncthreads();
+        unsigned long long before = carry_s;
+        for (unsigned w = 0; w < wave; ++w) before += wave_total[w];
+        for (int k = 0; k < MESH_SCAN_ITEMS; ++k)
+            if (i0 + k < len) counts[i0 + k] = before + (v - own) + item[k];
+        __syncthreads();
+        if (threadIdx.x == 255) carry_s = before + v;
+        __syncthreads();
+    }
+}
+
+__device__ inline uint64_t uniform64(uint64_t v) {
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    return ((uint64_t)hi << 32) | lo;
+}
+
+// the largest t in [lo, hi] with scan[t] <= g (scan[lo] <= g is given)
+__device__ inline uint32_t scan_find(const unsigned long long *__restrict__ scan, uint32_t lo, uint32_t hi, uint64_t g) {
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (scan[mid] <= g) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// Candidates [c_begin, c_end) of the slab [z0, z1], one per lane.  scan: the exclusive scan of the slab's counts.
+__global__ void __launch_bounds__(256) mesh_overlap_kernel(const Tri *__restrict__ tris,
+                                                           const unsigned long long *__restrict__ scan, uint32_t n_tri, int n,
+                                                           int z0, int z1, uint64_t c_begin, uint64_t c_end,
+                                                           uint32_t *__restrict__ grid, unsigned long long *__restrict__ hits) {
+    const uint64_t stride = (uint64_t)gridDim.x * 256u;
+    const unsigned lane = threadIdx.x & 63u;
+    unsigned long long wave_hits = 0;
+    for (uint64_t wb = uniform64(c_begin + (uint64_t)blockIdx.x * 256u + (threadIdx.x & ~63u)); wb < c_end; wb += stride) {
+        const uint64_t last = wb + 63 < c_end ? wb + 63 : c_end - 1;
+        const uint32_t t_first = scan_find(scan, 0, n_tri - 1, wb);         // wave-uniform
+        const uint32_t t_last = scan_find(scan, t_first, n_tri - 1, last);   // wave-uniform
+        const uint64_t g = wb + lane;
+        bool hit = false;
+        if (g <= last) {
+            const uint32_t ti = scan_find(scan, t_first, t_last, g);
+            const Tri &t = tris[ti];
+            const uint64_t local = g - scan[ti];
+            const uint32_t bx = (uint32_t)(t.bhi[0] - t.blo[0] + 1), by = (uint32_t)(t.bhi[1] - t.blo[1] + 1);
+            const uint64_t plane = (uint64_t)bx * by;
+            uint32_t ix, iy, iz;
+            if (((local | plane) >> 32) == 0) {
+                const uint32_t l = (uint32_t)local, p = (uint32_t)plane;
+                iz = l / p;
+                const uint32_t r = l - iz * p;
+                iy = r / bx;
+                ix = r - iy * bx;
+            } else {
+                iz = (uint32_t)(local / plane);
+                const uint64_t r = local - (uint64_t)iz * plane;
+                iy = (uint32_t)(r / bx);
+                ix = (uint32_t)(r - (uint64_t)iy * bx);
+            }
+            const int zl = t.blo[2] > z0 ? t.blo[2] : z0;
+            const int i[3] = { t.blo[0] + (int)ix, t.blo[1] + (int)iy, zl + (int)iz };
+            // inside the box and the slab by construction; the compare keeps a store inside the grid whatever the scan holds
+            hit = i[0] <= t.bhi[0] && i[1] <= t.bhi[1] && i[2] <= t.bhi[2] && i[2] <= z1 && svo_voxelize::overlaps(t, i);
+            if (hit) atomicMin(&grid[((size_t)(i[2] - z0) * n + (size_t)i[1]) * n + (size_t)i[0]], ti);
+        }
+        wave_hits += (unsigned long long)__popcll(__ballot(hit));
+    }
+    if (lane == 0 && wave_hits) atomicAdd(hits, wave_hits);
+}
+
+__global__ void __launch_bounds__(256) mesh_compact_kernel(const uint32_t *__restrict__ grid, int n, int z0, int zc,
+                                                           uint64_t *__restrict__ codes, uint32_t *__restrict__ owners,
+                                                           unsigned long long *__restrict__ counter, unsigned long long cap) {
+    // A block takes tiles of 1,024 cells (four per thread, a wave reads 256 contiguous bytes at a time), counts
+    // its occupied cells in LDS and reserves their list slots with ONE add on the global counter (Guideline 12):
+    // the counter still ends at the slab's count whatever the capacity, as the relaunch protocol needs.
+    constexpr int CELLS = 4;
+    __shared__ unsigned tile_count;
+    __shared__ unsigned long long tile_base;
+    const size_t total = (size_t)n * n * zc;
+    for (size_t base = (size_t)blockIdx.x * (256 * CELLS); base < total; base += (size_t)gridDim.x * (256 * CELLS)) {
+        if (threadIdx.x == 0) tile_count = 0;
+        __syncthreads();
+        uint32_t o[CELLS];
+        unsigned slot[CELLS];
+        for (int c = 0; c < CELLS; ++c) {
+            const size_t i = base + (size_t)c * 256 + threadIdx.x;
+            o[c] = i < total ? grid[i] : svo_voxelize::NO_OWNER;
+            slot[c] = o[c] != svo_voxelize::NO_OWNER ? atomicAdd(&tile_count, 1u) : 0u;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0 && tile_count) tile_base = atomicAdd(counter, (unsigned long long)tile_count);
+        __syncthreads();
+        for (int c = 0; c < CELLS; ++c) {
+            if (o[c] == svo_voxelize::NO_OWNER) continue;
+            const unsigned long long k = tile_base + slot[c];
+            if (k < cap) {
+                const size_t i = base + (size_t)c * 256 + threadIdx.x;
+                const uint32_t x = (uint32_t)(i % n), y = (uint32_t)((i / n) % n);
+                const uint32_t z = (uint32_t)z0 + (uint32_t)(i / ((size_t)n * n));
+                codes[k] = spread3(x) | (spread3(y) << 1) | (spread3(z) << 2);
+                owners[k] = o[c];
+            }
+        }
+    }
+}
+
+__global__ void mesh_attr_kernel(const Tri *__restrict__ tris, const uint32_t *__restrict__ idx, const float *__restrict__ col,
+                                 const uint64_t *__restrict__ codes, const uint32_t *__restrict__ owners, size_t count,
+                                 uint32_t flip, float *__restrict__ normals, float *__restrict__ colors) {
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (size_t)gridDim.x * blockDim.x) {
+        const uint32_t o = owners[i];
+        const Tri &t = tris[o];
+        float nrm[3];
+        svo_voxelize::leaf_normal(t, flip != 0, nrm);
+        normals[3 * i] = nrm[0];
+        normals[3 * i + 1] = nrm[1];
+        normals[3 * i + 2] = nrm[2];
+        if (col) {
+            const uint64_t code = codes[i];
+            const int v[3] = { (int)compact3(code), (int)compact3(code >> 1), (int)compact3(code >> 2) };
+            const size_t i0 = idx[3 * (size_t)o], i1 = idx[3 * (size_t)o + 1], i2 = idx[3 * (size_t)o + 2];
+            float c[3];
+            svo_voxelize::leaf_color(t, v, col + 3 * i0, col + 3 * i1, col + 3 * i2, c);
+            colors[3 * i] = c[0];
+            colors[3 * i + 1] = c[1];
+            colors[3 * i + 2] = c[2];
+        }
+    }
+}
+
+// svob_mesh is versioned by size like svob_limits; everything a launch would trust is checked here, on the host.
+int read_mesh(const svob_mesh *in, Mesh *out) {
+    *out = Mesh();
+    if (!in) return fail(SVOB_ERR_ARG, "null mesh");
+    if (in->size < 2 * sizeof(uint32_t)) return fail(SVOB_ERR_ARG, "svob_mesh.size must hold at least size and flags");
+    if (in->size > sizeof(svob_mesh))
+        return fail(SVOB_ERR_ARG, "svob_mesh.size " + std::to_string(in->size) + " is larger than this library's (" +
+                                      std::to_string(sizeof(svob_mesh)) + "): a newer ABI");
+    svob_mesh k;
+    std::memset(&k, 0, sizeof k);   // fields past the caller's size: zero (no triangles, no colours)
+    std::memcpy(&k, in, in->size);
+    if (k.flags & ~(uint32_t)SVOB_MESH_FLIP_WINDING) return fail(SVOB_ERR_ARG, "unknown svob_mesh.flags bits");
+    if (k.n_triangles >= 0xFFFFFFFFull) return fail(SVOB_ERR_ARG, "svob_mesh.n_triangles must be below 2^32 - 1");
+    if (k.n_vertices > 0xFFFFFFFFull) return fail(SVOB_ERR_ARG, "svob_mesh.n_vertices must fit 32 bits (the indices do)");
+    if (k.n_vertices && !k.positions) return fail(SVOB_ERR_ARG, "svob_mesh.positions is null");
+    if (k.n_triangles && !k.indices) return fail(SVOB_ERR_ARG, "svob_mesh.indices is null");
+    for (size_t i = 0; i < 3 * k.n_vertices; ++i)
+        if (!std::isfinite(k.positions[i]))
+            return fail(SVOB_ERR_ARG, "svob_mesh.positions: vertex " + std::to_string(i / 3) + " is not finite");
+    for (size_t i = 0; i < 3 * k.n_triangles; ++i)
+        if (k.indices[i] >= k.n_vertices)
+            return fail(SVOB_ERR_ARG, "svob_mesh.indices: triangle " + std::to_string(i / 3) + " names vertex " +
+                                          std::to_string(k.indices[i]) + " of " + std::to_string(k.n_vertices));
+    out->flags = k.flags;
+    out->positions = k.positions;
+    out->n_vertices = k.n_vertices;
+    out->indices = k.indices;
+    out->n_triangles = k.n_triangles;
+    out->colors = k.colors;
+    return SVOB_OK;
+}
+
+// Planes per z-slab of the owner grid (4 n^2 bytes a plane, no halo): clamp(cell_bytes / (4 n^2), 1, n), or
+// slab_rows.  A budget below one plane is an error, not an allocation beyond it.
+int mesh_slab_rows(int max_level, const Limits &lim, int *rows) {
+    const uint64_t n = 1ull << (max_level - 1);
+    const uint64_t plane = 4 * n * n;   // n <= 2^21: 2^44
+    if (plane > lim.cell_bytes)
+        return fail(SVOB_ERR_ARG, "max_level " + std::to_string(max_level) + ": one plane of the owner grid takes " +
+                                      std::to_string(plane) + " bytes, more than svob_limits.cell_bytes (" +
+                                      std::to_string(lim.cell_bytes) + ")");
+    if (lim.slab_rows > 0) *rows = (int)std::min<uint64_t>((uint64_t)lim.slab_rows, n);
+    else *rows = (int)std::min<uint64_t>(n, lim.cell_bytes / plane);
+    return SVOB_OK;
+}
+
+struct MeshLeaves {
+    std::vector<uint64_t> codes;
+    std::vector<uint32_t> owners;
+    std::vector<V3> normals, colors;   // colors: empty when the mesh has none
+};
+
+// svob_mesh_profile: device-event time per kernel of the calling thread's mesh builds.  Off by default (each
+// timed launch is followed by an event wait, which a build does not want).
+enum { MESH_K_SETUP, MESH_K_COUNT, MESH_K_SCAN, MESH_K_OVERLAP, MESH_K_COMPACT, MESH_K_ATTR, MESH_KERNELS };
+thread_local bool g_mesh_profile = false;
+thread_local double g_mesh_ms[MESH_KERNELS] = { 0, 0, 0, 0, 0, 0 };
+
+struct KernelClock {
+    bool on = false;
+    hipEvent_t a = nullptr, b = nullptr;
+    int slot = 0;
+    void open() {
+        on = g_mesh_profile && hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
+        if (on) for (double &v : g_mesh_ms) v = 0.0;
+    }
+    void begin(int s) {
+        slot = s;
+        if (on) (void)hipEventRecord(a, 0);
+    }
+    void end() {
+        if (!on) return;
+        float ms = 0.0f;
+        if (hipEventRecord(b, 0) == hipSuccess && hipEventSynchronize(b) == hipSuccess &&
+            hipEventElapsedTime(&ms, a, b) == hipSuccess)
+            g_mesh_ms[slot] += (double)ms;
+    }
+    ~KernelClock() {
+        if (a) (void)hipEventDestroy(a);
+        if (b) (void)hipEventDestroy(b);
+    }
+};
+
+void write_report(svob_report *rep, const svob_report &k0) {
+    if (!rep) return;   // rep->size was checked by the entry point
+    svob_report k = k0;
+    const size_t nb = std::min<size_t>(rep->size, sizeof k);
+    k.size = (uint32_t)nb;
+    std::memcpy(rep, &k, nb);
+}
+
+void write_stats(svob_mesh_stats *st, const svob_mesh_stats &k0) {
+    if (!st) return;
+    svob_mesh_stats k = k0;
+    const size_t nb = std::min<size_t>(st->size, sizeof k);
+    k.size = (uint32_t)nb;
+    std::memcpy(st, &k, nb);
+}
+
+int mesh_leaves_gpu(int device, const Mesh &mesh, int max_level, int rows, const Limits &lim, svob_report *rep,
+                    svob_mesh_stats *stats, MeshLeaves &out) {
+    const int depth = max_level - 1;
+    const int n = 1 << depth;
+    const uint32_t n_tri = (uint32_t)mesh.n_triangles;
+    svob_report r;
+    std::memset(&r, 0, sizeof r);
+    svob_mesh_stats s;
+    std::memset(&s, 0, sizeof s);
+    r.slab_rows = (uint32_t)rows;
+    size_t cap = lim.list_capacity ? (size_t)lim.list_capacity : std::max<size_t>(1 << 20, (size_t)n * n * 4);
+    r.list_capacity = cap;
+    out = MeshLeaves();
+    if (n_tri == 0) {   // nothing to launch
+        write_report(rep, r);
+        write_stats(stats, s);
+        return SVOB_OK;
+    }
+    HIPB(hipSetDevice(device));
+    float *dpos = nullptr, *dcol = nullptr, *dnrm = nullptr, *dleafcol = nullptr;
+    uint32_t *didx = nullptr, *grid = nullptr, *downers = nullptr;
+    Tri *dtris = nullptr;
+    unsigned long long *dscan = nullptr, *dstats = nullptr, *dcount = nullptr;
+    uint64_t *dcodes = nullptr;
+    auto cleanup = [&]() {
+        for (void *p : { (void *)dpos, (void *)dcol, (void *)dnrm, (void *)dleafcol, (void *)didx, (void *)grid,
+                         (void *)downers, (void *)dtris, (void *)dscan, (void *)dstats, (void *)dcount, (void *)dcodes })
+            if (p) (void)hipFree(p);
+    };
+    const size_t plane = (size_t)n * n;
+    hipError_t e = hipMalloc(&dpos, std::max<size_t>(1, mesh.n_vertices) * 3 * sizeof(float));
+    if (e == hipSuccess) e = hipMemcpy(dpos, mesh.positions, mesh.n_vertices * 3 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMalloc(&didx, (size_t)n_tri * 3 * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(didx, mesh.indices, (size_t)n_tri * 3 * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess && mesh.colors) {
+        e = hipMalloc(&dcol, mesh.n_vertices * 3 * sizeof(float));
+        if (e == hipSuccess) e = hipMemcpy(dcol, mesh.colors, mesh.n_vertices * 3 * sizeof(float), hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMalloc(&dtris, (size_t)n_tri * sizeof(Tri));
+    if (e == hipSuccess) e = hipMalloc(&dscan, ((size_t)n_tri + 1) * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&dstats, 4 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(dstats, 0, 4 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&dcount, sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMalloc(&grid, plane * (size_t)rows * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMalloc(&dcodes, cap * sizeof(uint64_t));
+    if (e == hipSuccess) e = hipMalloc(&downers, cap * sizeof(uint32_t));
+    if (e != hipSuccess) { cleanup(); return fail(SVOB_ERR_HIP, std::string("mesh alloc: ") + hipGetErrorString(e)); }
+
+    KernelClock clock;
+    clock.open();
+    clock.begin(MESH_K_SETUP);
+    hipLaunchKernelGGL(mesh_setup_kernel, dim3(blocks_for(n_tri, lim)), dim3(256), 0, 0, dpos, didx, n_tri, n, dtris, dstats);
+    clock.end();
+    e = hipGetLastError();
+    if (e != hipSuccess) { cleanup(); return fail(SVOB_ERR_HIP, std::string("mesh setup launch: ") + hipGetErrorString(e)); }
+
+    std::vector<std::pair<uint64_t, uint32_t>> leaves;
+    std::vector<uint64_t> hcodes;
+    std::vector<uint32_t> howners;
+    for (int z0 = 0; z0 < n; z0 += rows) {
+        const int zc = std::min(rows, n - z0);
+        const int z1 = z0 + zc - 1;
+        ++r.slabs;
+        clock.begin(MESH_K_COUNT);
+        hipLaunchKernelGGL(mesh_count_kernel, dim3(blocks_for((size_t)n_tri + 1, lim)), dim3(256), 0, 0, dtris, n_tri, z0, z1,
+                           dscan);
+        clock.end();
+        clock.begin(MESH_K_SCAN);
+        hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(256), 0, 0, dscan, (size_t)n_tri + 1);
+        clock.end();
+        e = hipGetLastError();
+        unsigned long long total = 0;
+        if (e == hipSuccess) e = hipMemcpy(&total, dscan + n_tri, sizeof total, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { cleanup(); return fail(SVOB_ERR_HIP, std::string("mesh count: ") + hipGetErrorString(e)); }
+        if (total == 0) continue;   // no triangle's box reaches this slab
+        e = hipMemset(grid, 0xFF, plane * (size_t)zc * sizeof(uint32_t));
+        for (uint64_t c0 = 0; e == hipSuccess && c0 < total; c0 += MESH_LAUNCH_CANDIDATES) {
+            const uint64_t c1 = std::min<uint64_t>(total, c0 + MESH_LAUNCH_CANDIDATES);   // 64-bit: a slab may hold more
+            clock.begin(MESH_K_OVERLAP);
+            hipLaunchKernelGGL(mesh_overlap_kernel, dim3(blocks_for((size_t)(c1 - c0), lim)), dim3(256), 0, 0, dtris, dscan,
+                               n_tri, n, z0, z1, c0, c1, grid, dstats + 3);
+            clock.end();
+            e = hipGetLastError();
+        }
+        if (e != hipSuccess) { cleanup(); return fail(SVOB_ERR_HIP, std::string("mesh overlap: ") + hipGetErrorString(e)); }
+        for (;;) {
+            e = hipMemset(dcount, 0, sizeof(unsigned long long));
+            if (e != hipSuccess) break;
+            clock.begin(MESH_K_COMPACT);
+            hipLaunchKernelGGL(mesh_compact_kernel, dim3(blocks_for((plane * (size_t)zc + 3) / 4, lim)), dim3(256), 0, 0, grid, n, z0, zc,
+                               dcodes, downers, dcount, (unsigned long long)cap);
+            clock.end();
+            e = hipGetLastError();
+            if (e != hipSuccess) break;
+            unsigned long long cnt = 0;
+            e = hipMemcpy(&cnt, dcount, sizeof(cnt), hipMemcpyDeviceToHost);
+            if (e != hipSuccess) break;
+            if (cnt <= cap) {
+                hcodes.resize(cnt);
+                howners.resize(cnt);
+                e = hipMemcpy(hcodes.data(), dcodes, cnt * sizeof(uint64_t), hipMemcpyDeviceToHost);
+                if (e == hipSuccess) e = hipMemcpy(howners.data(), downers, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost);
+                for (size_t i = 0; i < cnt; ++i) leaves.emplace_back(hcodes[i], howners[i]);
+                break;
+            }
+            // the kernel stored only the first cap leaves (k < cap): grow the list and compact again
+            (void)hipFree(dcodes);
+            (void)hipFree(downers);
+            dcodes = nullptr;
+            downers = nullptr;
+            cap = (size_t)(cnt * 1.25) + 1024;
+            ++r.relaunches;
+            e = hipMalloc(&dcodes, cap * sizeof(uint64_t));
+            if (e == hipSuccess) e = hipMalloc(&downers, cap * sizeof(uint32_t));
+            if (e != hipSuccess) break;
+        }
+        if (e != hipSuccess) { cleanup(); return fail(SVOB_ERR_HIP, std::string("mesh compact: ") + hipGetErrorString(e)); }
+    }
+    r.list_capacity = cap;
+    std::sort(leaves.begin(), leaves.end());   // each voxel appears once: the codes are unique
+    const size_t m = leaves.size();
+    out.codes.resize(m);
+    out.owners.resize(m);
+    for (size_t i = 0; i < m; ++i) {
+        out.codes[i] = leaves[i].first;
+        out.owners[i] = leaves[i].second;
+    }
+    out.normals.resize(m);
+    if (mesh.colors) out.colors.resize(m);
+    if (m) {
+        if (m > cap) {
+            (void)hipFree(dcodes);
+            (void)hipFree(downers);
+            dcodes = nullptr;
+            downers = nullptr;
+            e = hipMalloc(&dcodes, m * sizeof(uint64_t));
+            if (e == hipSuccess) e = hipMalloc(&downers, m * sizeof(uint32_t));
+            r.normals_regrown = 1;
+        }
+        if (e == hipSuccess) e = hipMemcpy(dcodes, out.codes.data(), m * sizeof(uint64_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMemcpy(downers, out.owners.data(), m * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMalloc(&dnrm, m * 3 * sizeof(float));
+        if (e == hipSuccess && mesh.colors) e = hipMalloc(&dleafcol, m * 3 * sizeof(float));
+        if (e == hipSuccess) {
+            clock.begin(MESH_K_ATTR);
+            hipLaunchKernelGGL(mesh_attr_kernel, dim3(blocks_for(m, lim)), dim3(256), 0, 0, dtris, didx, dcol, dcodes, downers, m,
+                               mesh.flags & (uint32_t)SVOB_MESH_FLIP_WINDING, dnrm, dleafcol);
+            clock.end();
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpy(out.normals.data(), dnrm, m * 3 * sizeof(float), hipMemcpyDeviceToHost);
+        if (e == hipSuccess && mesh.colors)
+            e = hipMemcpy(out.colors.data(), dleafcol, m * 3 * sizeof(float), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) { cleanup(); return fail(SVOB_ERR_HIP, std::string("mesh attributes: ") + hipGetErrorString(e)); }
+    }
+    unsigned long long hstats[4] = { 0, 0, 0, 0 };
+    e = hipMemcpy(hstats, dstats, sizeof hstats, hipMemcpyDeviceToHost);
+    cleanup();
+    if (e != hipSuccess) return fail(SVOB_ERR_HIP, std::string("mesh stats: ") + hipGetErrorString(e));
+    s.degenerate = hstats[0];
+    s.outside = hstats[1];
+    s.candidates = hstats[2];
+    s.overlaps = hstats[3];
+    write_report(rep, r);
+    write_stats(stats, s);
+    return SVOB_OK;
+}
+
+// What both mesh entry points check before a device is touched.
+int check_mesh_call(const svob_mesh *mesh, int max_level, const svob_limits *limits, const svob_report *report,
+                    const svob_mesh_stats *stats, Mesh *m, Limits *lim, int *rows) {
+    if (max_level < 2 || max_level > 22) return fail(SVOB_ERR_ARG, "max_level must be in [2, 22]");
+    int rc = read_mesh(mesh, m);
+    if (rc) return rc;
+    rc = read_limits(limits, lim);
+    if (rc) return rc;
+    if (report && report->size < sizeof(uint32_t)) return fail(SVOB_ERR_ARG, "svob_report.size must hold at least size");
+    if (stats && stats->size < sizeof(uint32_t)) return fail(SVOB_ERR_ARG, "svob_mesh_stats.size must hold at least size");
+    return mesh_slab_rows(max_level, *lim, rows);
+}
+
+
 // Empty tree: CompressSVO's placeholder descriptor 0 stays 0; the root's
 // attachment still encodes its default normal Vector3.up (Node ctor, Util.cs)
 // with no children (NaiveCreator.cs:132-136, 195-257).
@@ -928,5 +1430,79 @@ int svob_build_sampler_ex(int device, int sampler, int max_level, const svob_lim
                    (float)compact3_h(codes[i] >> 2) * inv };
     return layout_from_sorted(depth, codes, normals, col, out);
 }
+
+int svob_mesh_leaves(int device, const svob_mesh *mesh, int max_level, const svob_limits *limits, svob_report *report,
+                     svob_mesh_stats *stats, size_t *n_leaves, uint64_t **morton_out, float **normals_out,
+                     float **colors_out, uint32_t **owner_out) {
+    if (!n_leaves || !morton_out || !normals_out || !owner_out) return fail(SVOB_ERR_ARG, "null argument");
+    *n_leaves = 0;
+    *morton_out = nullptr;
+    *normals_out = nullptr;
+    *owner_out = nullptr;
+    if (colors_out) *colors_out = nullptr;
+    Mesh m;
+    Limits lim;
+    int rows = 0;
+    int rc = check_mesh_call(mesh, max_level, limits, report, stats, &m, &lim, &rows);
+    if (rc) return rc;
+    MeshLeaves L;
+    rc = mesh_leaves_gpu(device, m, max_level, rows, lim, report, stats, L);
+    if (rc) return rc;
+    const size_t k = L.codes.size(), k1 = std::max<size_t>(1, k);
+    *n_leaves = k;
+    *morton_out = (uint64_t *)std::malloc(k1 * sizeof(uint64_t));
+    *normals_out = (float *)std::malloc(k1 * 3 * sizeof(float));
+    *owner_out = (uint32_t *)std::malloc(k1 * sizeof(uint32_t));
+    const bool want_col = colors_out && m.colors;
+    if (want_col) *colors_out = (float *)std::malloc(k1 * 3 * sizeof(float));
+    if (!*morton_out || !*normals_out || !*owner_out || (want_col && !*colors_out)) {
+        std::free(*morton_out);
+        std::free(*normals_out);
+        std::free(*owner_out);
+        if (want_col) std::free(*colors_out);
+        *morton_out = nullptr;
+        *normals_out = nullptr;
+        *owner_out = nullptr;
+        if (colors_out) *colors_out = nullptr;
+        *n_leaves = 0;
+        return fail(SVOB_ERR_MEM, "out of host memory");
+    }
+    std::memcpy(*morton_out, L.codes.data(), k * sizeof(uint64_t));
+    std::memcpy(*normals_out, L.normals.data(), k * 3 * sizeof(float));
+    std::memcpy(*owner_out, L.owners.data(), k * sizeof(uint32_t));
+    if (want_col) std::memcpy(*colors_out, L.colors.data(), k * 3 * sizeof(float));
+    return SVOB_OK;
+}
+
+int svob_mesh_profile(int enable, double *ms_out) {
+    if (ms_out) std::memcpy(ms_out, g_mesh_ms, sizeof g_mesh_ms);
+    g_mesh_profile = enable != 0;
+    return SVOB_OK;
+}
+
+int svob_build_mesh(int device, const svob_mesh *mesh, int max_level, const svob_limits *limits, svob_report *report,
+                    svob_mesh_stats *stats, svob_result *out) {
+    if (!out) return fail(SVOB_ERR_ARG, "null out");
+    std::memset(out, 0, sizeof(*out));
+    Mesh m;
+    Limits lim;
+    int rows = 0;
+    int rc = check_mesh_call(mesh, max_level, limits, report, stats, &m, &lim, &rows);
+    if (rc) return rc;
+    MeshLeaves L;
+    rc = mesh_leaves_gpu(device, m, max_level, rows, lim, report, stats, L);
+    if (rc) return rc;
+    const int depth = max_level - 1;
+    if (L.codes.empty()) return empty_tree(depth, out);
+    if (!m.colors) {   // node.color = position - 1 (NaiveCreator.cs:66), as svob_build_from_leaves without colours
+        L.colors.resize(L.codes.size());
+        const float inv = std::ldexp(1.0f, -depth);
+        for (size_t i = 0; i < L.codes.size(); ++i)
+            L.colors[i] = { (float)compact3_h(L.codes[i]) * inv, (float)compact3_h(L.codes[i] >> 1) * inv,
+                            (float)compact3_h(L.codes[i] >> 2) * inv };
+    }
+    return layout_from_sorted(depth, L.codes, L.normals, L.colors, out);
+}
+
 
 }  // extern "C"

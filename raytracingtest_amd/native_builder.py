@@ -31,6 +31,20 @@ class _Report(ctypes.Structure):
                 ("list_capacity", ctypes.c_uint64)]
 
 
+class _Mesh(ctypes.Structure):
+    """svob_mesh (include/svo_build.h), versioned by size."""
+    _fields_ = [("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("positions", ctypes.c_void_p),
+                ("n_vertices", ctypes.c_size_t), ("indices", ctypes.c_void_p), ("n_triangles", ctypes.c_size_t),
+                ("colors", ctypes.c_void_p)]
+
+
+class _MeshStats(ctypes.Structure):
+    _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("degenerate", ctypes.c_uint64),
+                ("outside", ctypes.c_uint64), ("candidates", ctypes.c_uint64), ("overlaps", ctypes.c_uint64)]
+
+
+MESH_FLIP_WINDING = 1
+MESH_STATS_FIELDS = ("degenerate", "outside", "candidates", "overlaps")
 LIMIT_FIELDS = ("cell_bytes", "slab_rows", "list_capacity", "max_blocks")
 REPORT_FIELDS = ("slabs", "slab_rows", "relaunches", "normals_regrown", "list_capacity")
 
@@ -74,15 +88,21 @@ def blib():
         L.svob_surface_leaves_ex.argtypes = [i, i, i, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(vp),
                                              ctypes.POINTER(vp)]
         L.svob_slab_rows.argtypes = [i, vp]
+        L.svob_build_mesh.argtypes = [i, vp, i, vp, vp, vp, ctypes.POINTER(_Result)]
+        L.svob_mesh_leaves.argtypes = [i, vp, i, vp, vp, vp, ctypes.POINTER(sz), ctypes.POINTER(vp), ctypes.POINTER(vp),
+                                       ctypes.POINTER(vp), ctypes.POINTER(vp)]
         L.svob_eval_sampler.argtypes = [i, sz, vp, vp]
         L.svob_opensimplex_table.argtypes = [vp]
+        L.svob_mesh_profile.argtypes = [i, vp]
+        L.svob_mesh_profile.restype = i
         L.svob_free.argtypes = [ctypes.POINTER(_Result)]
         L.svob_free.restype = None
         L.svob_free_ptr.argtypes = [vp]
         L.svob_free_ptr.restype = None
         L.svob_last_error.restype = ctypes.c_char_p
         for name in ("svob_build_sampler", "svob_build_from_leaves", "svob_surface_leaves", "svob_eval_sampler",
-                     "svob_opensimplex_table", "svob_build_sampler_ex", "svob_surface_leaves_ex", "svob_slab_rows"):
+                     "svob_opensimplex_table", "svob_build_sampler_ex", "svob_surface_leaves_ex", "svob_slab_rows",
+                     "svob_build_mesh", "svob_mesh_leaves"):
             getattr(L, name).restype = i
         _blib = L
     return _blib
@@ -161,6 +181,89 @@ def surface_leaves(sample_type, max_level, device=0, limits=None, report=False):
     finally:
         blib().svob_free_ptr(mp)
         blib().svob_free_ptr(npp)
+
+
+def _mesh(positions, triangles, colors, flip):
+    """A svob_mesh over contiguous copies of the arrays; returns (struct, the arrays it points into)."""
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    tri = np.asarray(triangles).reshape(-1, 3)
+    if tri.size and (tri.min() < 0 or tri.max() > 0xFFFFFFFF):
+        raise SvoError("triangle indices must fit uint32")
+    tri = np.ascontiguousarray(tri, np.uint32)
+    col = None if colors is None else np.ascontiguousarray(colors, np.float32).reshape(-1, 3)
+    if col is not None and len(col) != len(pos):
+        raise SvoError(f"colors holds {len(col)} rgb for {len(pos)} vertices")
+    m = _Mesh(size=ctypes.sizeof(_Mesh), flags=MESH_FLIP_WINDING if flip else 0, positions=pos.ctypes.data,
+              n_vertices=len(pos), indices=tri.ctypes.data, n_triangles=len(tri),
+              colors=None if col is None else col.ctypes.data)
+    return m, (pos, tri, col)
+
+
+def _stats_dict(st):
+    return {k: int(getattr(st, k)) for k in MESH_STATS_FIELDS}
+
+
+def build_mesh_svo(positions, triangles, max_level, colors=None, flip=False, device=0, prefer_v1=True, limits=None,
+                   report=False):
+    """svob_build_mesh: an indexed triangle mesh (positions [v, 3] in the cube's unit frame [0,1]^3, triangles
+    [t, 3], optional per-vertex rgb) voxelised on the GPU by the rule of voxelize.py and laid out as
+    build_from_leaves does.  flip: SVOB_MESH_FLIP_WINDING.  limits: as build_sampler_svo (they never change the
+    result).  report=True: returns (svo, dict of REPORT_FIELDS, dict of MESH_STATS_FIELDS)."""
+    m, keep = _mesh(positions, triangles, colors, flip)
+    res = _Result()
+    rep = _new_report()
+    st = _MeshStats(size=ctypes.sizeof(_MeshStats))
+    _check(blib().svob_build_mesh(int(device), ctypes.byref(m), int(max_level), _limits(limits), ctypes.byref(rep),
+                                  ctypes.byref(st), ctypes.byref(res)), "svob_build_mesh")
+    del keep
+    try:
+        data = _to_svodata(res, prefer_v1)
+        data.n_leaves = int(res.n_leaves)
+        return (data, _report_dict(rep), _stats_dict(st)) if report else data
+    finally:
+        blib().svob_free(ctypes.byref(res))
+
+
+MESH_KERNELS = ("setup", "count", "scan", "overlap", "compact", "attributes")
+
+
+def mesh_profile(enable):
+    """svob_mesh_profile: switch the per-kernel device-event timing of this thread's mesh calls; returns the
+    sums of the last timed call, {kernel: milliseconds}."""
+    ms = (ctypes.c_double * len(MESH_KERNELS))()
+    _check(blib().svob_mesh_profile(1 if enable else 0, ms), "svob_mesh_profile")
+    return dict(zip(MESH_KERNELS, (float(v) for v in ms)))
+
+
+def mesh_leaves(positions, triangles, max_level, colors=None, flip=False, device=0, limits=None, report=False):
+    """svob_mesh_leaves: (Morton codes uint64[m] sorted, normals float32[m, 3], colours float32[m, 3] or None,
+    owner uint32[m]) -- voxelize.voxelize's result at depth max_level - 1, from the GPU; with report=True two more
+    items, the dicts of REPORT_FIELDS and MESH_STATS_FIELDS."""
+    m, keep = _mesh(positions, triangles, colors, flip)
+    n = ctypes.c_size_t()
+    ptrs = [ctypes.c_void_p() for _ in range(4)]   # morton, normals, colours, owner
+    rep = _new_report()
+    st = _MeshStats(size=ctypes.sizeof(_MeshStats))
+    _check(blib().svob_mesh_leaves(int(device), ctypes.byref(m), int(max_level), _limits(limits), ctypes.byref(rep),
+                                   ctypes.byref(st), ctypes.byref(n), *[ctypes.byref(p) for p in ptrs]),
+           "svob_mesh_leaves")
+    del keep
+    try:
+        k = n.value
+
+        def arr(p, ctype, shape, dtype):
+            if not k:
+                return np.zeros(shape, dtype)
+            return np.ctypeslib.as_array(ctypes.cast(p, ctypes.POINTER(ctype)), shape=shape).copy()
+        codes = arr(ptrs[0], ctypes.c_uint64, (k,), np.uint64)
+        nrm = arr(ptrs[1], ctypes.c_float, (k, 3), np.float32)
+        col = arr(ptrs[2], ctypes.c_float, (k, 3), np.float32) if ptrs[2].value else None
+        owner = arr(ptrs[3], ctypes.c_uint32, (k,), np.uint32)
+        out = (codes, nrm, col, owner)
+        return out + (_report_dict(rep), _stats_dict(st)) if report else out
+    finally:
+        for p in ptrs:
+            blib().svob_free_ptr(p)
 
 
 def eval_sampler(sample_type, xyz):

@@ -168,6 +168,23 @@ public static class SvoNative {
     }
     [DllImport(Builder)] public static extern int svob_build_sampler(int device, int sampler, int maxLevel,
                                                                      out SvobResult result);
+    // Meshes (include/svo_build.h "Triangle meshes"): positions in the cube's unit frame [0,1]^3
+    public const uint MeshFlipWinding = 1;   // SVOB_MESH_FLIP_WINDING: Unity's front faces are clockwise
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvobMesh {     // == svob_mesh, 48 bytes, versioned by size
+        public uint size, flags;
+        public IntPtr positions; public UIntPtr nVertices;    // float xyz per vertex
+        public IntPtr indices; public UIntPtr nTriangles;     // 3 uint per triangle
+        public IntPtr colors;                                 // float rgb per vertex, or zero
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvobMeshStats {   // == svob_mesh_stats, 40 bytes
+        public uint size, reserved;
+        public ulong degenerate, outside, candidates, overlaps;
+    }
+    // limits and report: IntPtr.Zero for the defaults / no report
+    [DllImport(Builder)] public static extern int svob_build_mesh(int device, ref SvobMesh mesh, int maxLevel, IntPtr limits,
+                                                                  IntPtr report, ref SvobMeshStats stats, out SvobResult result);
     [DllImport(Builder)] public static extern void svob_free(ref SvobResult result);
     [DllImport(Builder)] public static extern IntPtr svob_last_error();
 
@@ -372,6 +389,61 @@ public class RaytracingMasterNative : MonoBehaviour {
         }
         _stackMode = SvoNative.StackModeFor(_ctx);
         _currentSample = 0;
+    }
+
+    // A Unity Mesh as a pool behind the terrain: its bounds are mapped uniformly into the unit cube with a 2 %
+    // margin, svob_build_mesh voxelises it on GPU 0 at maxLevel, and the pool is uploaded at node dstOffset in the
+    // wide format -- place it with SetObjects (root = dstOffset).  Unity's front faces are clockwise in its
+    // left-handed frame: the winding flag keeps the normals outward.  Returns the pool's node count.
+    public ulong SetSVOFromMesh(Mesh mesh, int maxLevel, ulong dstOffset) {
+        Vector3[] verts = mesh.vertices;
+        int[] tris = mesh.triangles;
+        Color[] cols = mesh.colors;
+        Bounds b = mesh.bounds;
+        float extent = Mathf.Max(b.size.x, Mathf.Max(b.size.y, b.size.z));
+        float scale = extent > 0f ? 0.96f / extent : 1f;
+        var pos = new float[3 * verts.Length];
+        for (int i = 0; i < verts.Length; ++i) {
+            Vector3 p = (verts[i] - b.center) * scale;
+            pos[3 * i] = 0.5f + p.x; pos[3 * i + 1] = 0.5f + p.y; pos[3 * i + 2] = 0.5f + p.z;
+        }
+        var idx = new uint[tris.Length];
+        for (int i = 0; i < tris.Length; ++i) idx[i] = (uint)tris[i];
+        float[] rgb = null;
+        if (cols != null && cols.Length == verts.Length) {
+            rgb = new float[3 * cols.Length];
+            for (int i = 0; i < cols.Length; ++i) { rgb[3 * i] = cols[i].r; rgb[3 * i + 1] = cols[i].g; rgb[3 * i + 2] = cols[i].b; }
+        }
+        GCHandle hp = GCHandle.Alloc(pos, GCHandleType.Pinned), hi = GCHandle.Alloc(idx, GCHandleType.Pinned);
+        GCHandle hc = rgb != null ? GCHandle.Alloc(rgb, GCHandleType.Pinned) : default(GCHandle);
+        try {
+            var m = new SvoNative.SvobMesh {
+                size = (uint)Marshal.SizeOf(typeof(SvoNative.SvobMesh)), flags = SvoNative.MeshFlipWinding,
+                positions = hp.AddrOfPinnedObject(), nVertices = (UIntPtr)verts.Length,
+                indices = hi.AddrOfPinnedObject(), nTriangles = (UIntPtr)(tris.Length / 3),
+                colors = rgb != null ? hc.AddrOfPinnedObject() : IntPtr.Zero };
+            var stats = new SvoNative.SvobMeshStats { size = (uint)Marshal.SizeOf(typeof(SvoNative.SvobMeshStats)) };
+            SvoNative.CheckBuild(SvoNative.svob_build_mesh(0, ref m, maxLevel, IntPtr.Zero, IntPtr.Zero, ref stats, out var r),
+                                 "svob_build_mesh");
+            try {
+                ulong n = (ulong)r.nNodes;
+                // wide nodes hold ABSOLUTE first-child indices: a pool that does not start at node 0 is rebased
+                for (ulong i = 0; dstOffset != 0 && i < n; ++i) {
+                    long node = Marshal.ReadInt64(r.nodes, (int)(8 * i));
+                    if ((node & 0xFF) != 0) Marshal.WriteInt64(r.nodes, (int)(8 * i), node + ((long)dstOffset << 32));
+                }
+                SvoNative.Check(SvoNative.svo_set_buffer_v2(_ctx, r.nodes, r.nNodes, r.attachments, (UIntPtr)(2 * n),
+                                                            (UIntPtr)dstOffset), "svo_set_buffer_v2");
+                _stackMode = SvoNative.StackModeFor(_ctx);
+                _currentSample = 0;
+                return n;
+            } finally {
+                SvoNative.svob_free(ref r);
+            }
+        } finally {
+            hp.Free(); hi.Free();
+            if (rgb != null) hc.Free();
+        }
     }
 
     // RaytracingMaster.cs:118-135 (attachments land at 2*offset: the reference's offset bug is fixed)
