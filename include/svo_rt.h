@@ -340,6 +340,7 @@ int svo_beam_starts(svo_ctx *ctx, int width, int height, const svo_band *band, f
  * origin = world hit point + 0.001 * normal; an occluded pixel gets hit flag
  * bit 3 and a black Result. */
 enum { SVO_OPT_SHADOW_RAYS = 1, SVO_OPT_KERNEL_TIMING = 2, SVO_OPT_COUNT_BEAM = 4 };
+enum { SVO_OPT_SCENE_SHADOWS = 8 };   /* svo_set_options: shadow and light passes know the objects (below) */
 int svo_set_options(svo_ctx *ctx, uint32_t options);
 
 /* SVO_OPT_KERNEL_TIMING: every render launch brackets its primary-ray kernel
@@ -829,9 +830,10 @@ int svo_light_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t fl
  * svo_render_progressive(_async); it combines with a skybox texture.  svo_count_fetches, svo_beam_starts and
  * svo_assemble_frame are unaffected; a compact part rebuilds an object pixel's normal from `parent`
  * UNROTATED, so a one-process-per-GPU split with objects sends dense RGB parts.  Stated limits, each
- * SVO_ERR_STATE before anything is enqueued: a render with a non-empty list and SVO_OPT_SHADOW_RAYS,
- * reflection, an ambient term, lights or LOD, svo_render_samples with objects; and a non-empty list on a
- * multi-device context (refused by svo_set_objects).  svo_get_objects: copies min(cap, n) objects,
+ * SVO_ERR_STATE before anything is enqueued: a render with a non-empty list and reflection, an ambient term
+ * or LOD, svo_render_samples with objects; a render with a non-empty list and SVO_OPT_SHADOW_RAYS or lights
+ * unless SVO_OPT_SCENE_SHADOWS is set ("Objects in light" below); and a non-empty list on a multi-device
+ * context (refused by svo_set_objects).  svo_get_objects: copies min(cap, n) objects,
  * *n_objects = n; pointers nullable. */
 typedef struct svo_object {     /* 64 bytes */
     uint32_t root;              /* descriptor index of the object's root in the context's pool */
@@ -855,6 +857,76 @@ int svo_trace_scene(svo_ctx *ctx, const svo_ray *d_rays, size_t n, int stack_mod
 int svo_trace_scene_host(svo_ctx *ctx, const svo_ray *rays, size_t n, int stack_mode, uint32_t flags,
                          const svo_object *objects, int n_objects, svo_hit *hits, float *position, uint64_t *voxel,
                          int32_t *object);
+
+/* Objects in light: the light rule for the records of a scene query, whose hit may lie on a placed object,
+ * a rotated and scaled voxel (csrc/svo_scene_light.h; numpy: scene_light.py).  Every operation is one IEEE
+ * f32 rounding, no fma; only + - * /, sqrt, compares and selects.
+ *  (a) Origin and face of a scene hit, from the traced world ray (o, d) AS GIVEN to svo_trace_scene, the
+ *      record (t, hit_scale, the world normal n), the voxel key (object-local) and the object id:
+ *       - id -1, an id outside -1 .. n_objects, or a record without flag bit 0: nothing; every light gets
+ *         the dead ray.  No table entry is read for such an id.
+ *       - id 0 (terrain): the light rule unchanged; its steps 1-2 give Q, g and out.
+ *       - id c + 1, ob = objects[c] = (k, p, R):
+ *          1. (o', d') = step 2 of the object rule from the world ray as given, then the small-direction
+ *             clamp on d' unless SVO_QUERY_RAW_DIRECTIONS: the ray the scene query walked in the object.
+ *          2. (g, out, Q') = steps 1-3 of the bounce rule on (o', d', t, hit_scale, key).  The parameter t is
+ *             shared between the frames and the object frame's cube is the world convention's [-16, 16]^3.
+ *          3. Q_i = (((R_i0 Q'_0 + R_i1 Q'_1) + R_i2 Q'_2) 2^k) + p_i (2^k is exact); N_i = out R_ig
+ *             (exact): the entered face's outward normal in world space.
+ *  (b) Toward a light (p_l, range, colour): L = p_l - Q.  An object hit is facing iff
+ *      (N_0 L_0 + N_1 L_1) + N_2 L_2 > 0 (ordered); the terrain keeps L_g out > 0.  d2, u and "in range" are
+ *      the light rule's step 3.  Not facing, or out of range: the dead ray.  Otherwise the ray is
+ *      {Q, t_max 1, L, 0}, and the light's factor is the light rule's step 6 with the record's world normal.
+ *
+ * svo_scene_light_rays is svo_light_rays for the results of svo_trace_scene: out[i n_lights + j] = the
+ * world-space shadow ray of hit i toward lights[j], or svo_bounce_rays' dead ray.  d_object: the ids
+ * svo_trace_scene wrote (n int32, 4-byte aligned).  objects (0 .. 8, the list the batch was traced with; the
+ * roots are not read or checked) and lights (1 .. 8; flags not read) are HOST arrays, copied before the call
+ * returns.  flags: SVO_QUERY_RAW_DIRECTIONS only (how rays[i] was traced).  n n_lights <= 2^31 - 1.  Writes
+ * nothing past n n_lights entries; the output must not overlap an input (SVO_ERR_ARG).  The argument checks
+ * are svo_light_rays' and svo_trace_scene's, with their messages, before any device is touched; n == 0:
+ * SVO_OK, nothing launched.  Reads no pool.  Ray lists 16-byte aligned, records and keys 8-byte.  A
+ * multi-device context runs it on devices[0].  Asynchronous on `stream`; the host form blocks.  Tracing the
+ * output with svo_trace_scene (flags 0, the same objects) gives the occlusion of each light over the whole
+ * scene: lit iff the record has neither flag bit 0 nor bit 4.
+ *
+ *  (c) Occlusion over the scene.  A secondary ray is occluded iff the record svo_trace_scene gives for it --
+ *      over the terrain and the context's objects, with the same flags and stack mode -- has flag bit 0.
+ *      (That bit needs no nearest hit: it is "the terrain candidate hits, or some object whose cube span
+ *      test t_in <= t_out holds for a valid object ray hits after the t_max filter", so the passes stop a
+ *      ray at its first hit.)
+ *  (d) In renders.  SVO_OPT_SCENE_SHADOWS (svo_set_options bit 8; off by default, and with it off every byte
+ *      and every refusal is what it was) lets the shadow and the light pass know the objects.  With the bit
+ *      set, a non-empty object list and SVO_OPT_SHADOW_RAYS and / or lights: the primary launch takes exactly
+ *      the path it takes with neither (no fused shadows, whatever svo_config.shadow_form says: all three
+ *      forms give the same bytes); the object pass follows; then, over the hit pixels of the finished
+ *      records (the hit masks after the object pass),
+ *       - the directional shadow: the shadow ray above, P + 0.001 n from the record (world normal) and the
+ *         camera ray, direction -light, traced as given (raw, t_max +inf).  A ray the query's classify calls
+ *         invalid is not traced and leaves the pixel lit; an occluded pixel gets flag bit 3 in hits and
+ *         compact and the black Result in every colour output.  The reference's P + 0.001 n self-hit is kept
+ *         as the terrain has it: an object pixel is very often shadowed by its own object.
+ *       - the lights: step 7's fold of the light rule with (a)-(c): the ray {Q, 1, L} is traced with flags 0
+ *         (clamped; shading keeps L); lit iff its record has neither flag bit 0 nor bit 4;
+ *         SVO_LIGHT_NO_SHADOW skips the walk; res starts from the pixel's direct colour, black with bit 3;
+ *         the albedo is the record's (att[parent] at hit_idx; parent is the absolute pool index).
+ *      The sky pass comes last.  Only the outputs the shadow and light passes change without objects are
+ *      changed.  With the bit set and an empty list every launch takes the path and writes the bytes it does
+ *      with the bit clear.  Every occlusion walk is the guarded loop on the 21-slot stack.  The opt-in is
+ *      also honest about cost: every shadow ray may walk up to eight more cubes.  The bit is harmless on a
+ *      multi-device context (svo_set_objects refuses a non-empty list there).
+ *
+ * Out of scope, each SVO_ERR_STATE or SVO_ERR_ARG as before where it can be asked for: objects in bounce and
+ * ambient rays (objects with reflection or an ambient term stay refused, with the bit set too); objects under
+ * LOD and svo_render_samples; objects on multi-device contexts; an early exit at the light or at a radius;
+ * SVO_QUERY_ORDERED for scene queries; more than eight objects, or an index over them; a directional shadow
+ * ray that avoids the P + 0.001 n self-hit. */
+int svo_scene_light_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
+                         const uint64_t *d_voxel, const int32_t *d_object, const svo_object *objects, int n_objects,
+                         const svo_light *lights, int n_lights, svo_ray *d_rays_out, void *stream);
+int svo_scene_light_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
+                              const uint64_t *voxel, const int32_t *object, const svo_object *objects, int n_objects,
+                              const svo_light *lights, int n_lights, svo_ray *rays_out);
 
 /* Information about the uploaded pool. */
 int svo_get_info(svo_ctx *ctx, size_t *n_nodes, int *max_depth, int *device);

@@ -42,7 +42,7 @@ EXPORTS = ("svo_create", "svo_set_buffer", "svo_set_buffer_v2", "svo_set_camera"
            "svo_sample_sky_host", "svo_set_ambient", "svo_get_ambient", "svo_ambient_rays", "svo_ambient_rays_host",
            "svo_set_lights", "svo_get_lights", "svo_light_rays", "svo_light_rays_host",
            "svo_set_objects", "svo_get_objects", "svo_object_rays", "svo_object_rays_host", "svo_trace_scene",
-           "svo_trace_scene_host")
+           "svo_trace_scene_host", "svo_scene_light_rays", "svo_scene_light_rays_host")
 # svo_ray: one caller-supplied ray of svo_trace_rays (world space, direction used as given)
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")])
 assert RAY_DTYPE.itemsize == 32
@@ -65,6 +65,7 @@ SCENE_NO_TERRAIN = 4                         # svo_trace_scene flags: the terrai
 SVO_OPT_SHADOW_RAYS = 1
 SVO_OPT_KERNEL_TIMING = 2
 SVO_OPT_COUNT_BEAM = 4
+SVO_OPT_SCENE_SHADOWS = 8   # the shadow and light passes know the placed objects
 LAYOUT_BAND, LAYOUT_FRAME = 0, 1
 PART_COMPACT, PART_RGBA8, PART_RGB8, PART_SPARSE_RGB8 = 0, 1, 2, 3
 LINK_SELF, LINK_PEER, LINK_COPY = 0, 1, 2
@@ -233,6 +234,8 @@ def lib():
         "svo_object_rays_host": [vp, vp, sz, ctypes.c_uint32, vp, vp],
         "svo_trace_scene": [vp, vp, sz, i, ctypes.c_uint32, vp, i, ctypes.POINTER(SvoQueryOut), vp, vp],
         "svo_trace_scene_host": [vp, vp, sz, i, ctypes.c_uint32, vp, i, vp, vp, vp, vp],
+        "svo_scene_light_rays": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp, i, vp, i, vp, vp],
+        "svo_scene_light_rays_host": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp, i, vp, i, vp],
         "svo_destroy": [vp],
         "svo_last_error": [],
         "svo_abi_version": [],

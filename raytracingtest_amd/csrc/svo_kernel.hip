@@ -16,6 +16,7 @@
 #include "svo_ambient.h"
 #include "svo_light.h"
 #include "svo_object.h"
+#include "svo_scene_light.h"
 
 #include <hipcub/hipcub.hpp>   // ordered ray queries: the toolchain's device radix sort (launch_query_sort)
 
@@ -2131,6 +2132,51 @@ __global__ __launch_bounds__(256) void object_rays_kernel(const QueryRay *rays, 
     dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
 }
 
+// svo_scene_light_rays (svo_scene_light.h is the rule): entry e = i * n_lights + j of the
+// output is the world-space shadow ray of the scene hit i toward light j.  One thread per entry, two 16-byte
+// stores; the output is n_lights times the input and must not overlap it (checked by the host).  Reads no
+// pool: an object's root is not read.  The object table and the lights are one kernel argument; a lane's
+// object and light come out of it by selects over the eight entries (id and j differ between lanes), so no
+// entry is ever addressed by a lane's value and an id outside 0 .. n_objects reads nothing.
+struct SceneLightKernelArgs {
+    svo_objects::Object o[svo_objects::MAX_OBJECTS];
+    svo_lights::Light l[svo_lights::MAX_LIGHTS];
+    int n_objects, n_lights;
+};
+
+__global__ __launch_bounds__(256) void scene_light_rays_kernel(const QueryRay *__restrict__ rays, uint32_t n, uint32_t flags,
+                                                               const Hit *__restrict__ hits,
+                                                               const unsigned long long *__restrict__ voxel,
+                                                               const int32_t *__restrict__ object_id, SceneLightKernelArgs a,
+                                                               QueryRay *__restrict__ out) {
+    const size_t e = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (e >= (size_t)n * (size_t)a.n_lights) return;
+    const uint32_t i = (uint32_t)(e / (uint32_t)a.n_lights);
+    const int j = (int)(e - (size_t)i * (uint32_t)a.n_lights);
+    const uint4 *src = reinterpret_cast<const uint4 *>(rays) + 2 * (size_t)i;
+    const uint4 ra = src[0], rb = src[1];
+    const uint2 *rec = reinterpret_cast<const uint2 *>(hits + i);
+    const uint2 h0 = rec[0], h1 = rec[1], h2 = rec[2];
+    const uint32_t ray[8] = { ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w };
+    const uint32_t hit[6] = { h0.x, h0.y, h1.x, h1.y, h2.x, h2.y };
+    const int32_t id = object_id[i];
+    svo_lights::Light l = a.l[0];
+#pragma unroll
+    for (int q = 1; q < svo_lights::MAX_LIGHTS; ++q)
+        if (j == q) l = a.l[q];
+    svo_objects::Object ob = a.o[0];
+#pragma unroll
+    for (int q = 1; q < svo_objects::MAX_OBJECTS; ++q)
+        if (id == q + 1) ob = a.o[q];
+    // the rule on a table of the lane's own object: id 0 stays the terrain, c + 1 becomes 1, the rest -1
+    const int32_t local = id < 0 || id > a.n_objects ? -1 : id > 0 ? 1 : 0;
+    uint32_t o[8];
+    svo_scene_light::scene_light_entry(ray, hit, voxel[i], local, (flags & QUERY_RAW) != 0, &ob, 1, l, o, nullptr);
+    uint4 *dst = reinterpret_cast<uint4 *>(out) + 2 * e;
+    dst[0] = make_uint4(o[0], o[1], o[2], o[3]);
+    dst[1] = make_uint4(o[4], o[5], o[6], o[7]);
+}
+
 // Steps 2-4 of the rule for one lane and one object (wave-uniform `ob`): the clamped object ray (o2, d2),
 // its setup and whether the lane walks the object.  live: the lane has a valid world ray (o, d).
 __device__ __forceinline__ bool object_setup(const svo_objects::Object &ob, bool live, const float o[3], const float d[3],
@@ -2259,9 +2305,14 @@ __global__ __launch_bounds__(TILE) void scene_rays_kernel(LaunchParams p, QueryA
 // rule over the objects; a pixel whose best changed gets every output of the launch rewritten at the
 // render's own addresses, and its bit or-ed into the tile's hit-mask word (masks: the caller's or the sky
 // pass's scratch, nullable), so a sky pass behind this one leaves it alone.  Untouched pixels keep every byte.
-template <int MODE>
+// ids (the scene-aware light pass's input, indexed as the launch's outputs; null without IDS): for every pixel
+// inside the frame 0 where the primary record stood (the terrain, or a miss) and j + 1 where object j took it.
+// IDS is a template parameter so that the pass without the output is the code it was (it was 1 % slower with a
+// run-time test: tools/objects_bench.py against the parent commit's library).
+template <int MODE, bool IDS>
 __global__ __launch_bounds__(TILE) void object_pass_kernel(LaunchParams p, ObjectKernelArgs a,
-                                                           unsigned long long *__restrict__ masks, int tiles_x) {
+                                                           unsigned long long *__restrict__ masks, int tiles_x,
+                                                           uint8_t *__restrict__ ids) {
     extern __shared__ uint2 stk_base[];
     const int lane = (int)threadIdx.x;
     const int t = (int)blockIdx.x;
@@ -2293,6 +2344,7 @@ __global__ __launch_bounds__(TILE) void object_pass_kernel(LaunchParams p, Objec
     Record best;
     miss_record(best, 0u);
     bool changed = false;
+    int best_id = 0;
     uint2 *stk = stk_base + lane;
 #pragma nounroll
     for (int j = 0; j < a.n; ++j) {
@@ -2309,14 +2361,133 @@ __global__ __launch_bounds__(TILE) void object_pass_kernel(LaunchParams p, Objec
                 best_hit = true;
                 best_t = __uint_as_float(cand.w[2]);
                 changed = true;
+                if (IDS) best_id = j + 1;
             }
         }
     }
     if (changed) store_outputs(p.out, i, best);
+    if (IDS && inside) ids[i] = (uint8_t)best_id;
     if (masks) {
         const lmask m = LM_OF(changed);
         if (m != 0 && lane == 0) masks[t] |= m;
     }
+}
+
+// ------------------------------------------------- objects in shadow and light
+// SVO_OPT_SCENE_SHADOWS: the shadow and light passes of a render with placed objects, in
+// the list-pass frame behind the object pass.  A secondary ray is occluded iff the record svo_trace_scene
+// gives for it has flag bit 0, and that bit needs no nearest hit: it is "the terrain candidate hits, or some
+// object whose cube span test t_in <= t_out holds for a valid object ray hits after the t_max filter" --
+// cube_test's `t_entry < best.t` half only ever skips an object once a hit exists.  So a lane stops at its
+// first hit, and an object is skipped for a wave whose lanes are all decided.
+
+// Is the world ray (o, d, t_lim) occluded by the terrain or an object of the table?  live: the lane has a
+// ray, and it is valid by the query's classify.  Every walk is the guarded loop on the 21-slot stack, as in
+// scene_rays_kernel; the loop over the table is wave-uniform and a walk runs under `if (go)` only when the
+// wave's ballot of go is non-zero.
+template <int MODE>
+__device__ __forceinline__ bool scene_occluded(const LaunchParams &p, const ObjectKernelArgs &a, bool live, const float o[3],
+                                               const float d[3], bool raw, float t_lim, uint2 *__restrict__ stk) {
+    bool occluded = false;
+    if (LM_OF(live) != 0) {   // wave-uniform
+        if (live) {
+            float o2[3] = {o[0], o[1], o[2]}, d2[3] = {d[0], d[1], d[2]};
+            svo_reflect::clamp_direction(d2, raw);
+            Ray r;
+            setup_ray(o2, d2, r);
+            Record c;
+            occluded = candidate_walk<MODE>(p, r, 0u, false, a.o[0].rotation, o2, d2, t_lim, false, false, stk, c);
+        }
+    }
+#pragma nounroll
+    for (int j = 0; j < a.n; ++j) {
+        const svo_objects::Object &ob = a.o[j];   // uniform j: scalar loads
+        float o2[3], d2[3];
+        Ray r;
+        const bool go = live && !occluded && object_setup(ob, live, o, d, raw, false, 0.0f, o2, d2, r);
+        if (LM_OF(go) == 0) continue;   // wave-uniform
+        if (go) {
+            Record c;
+            occluded = candidate_walk<MODE>(p, r, ob.root, true, ob.rotation, o2, d2, t_lim, false, false, stk, c);
+        }
+    }
+    return occluded;
+}
+
+// The directional shadow over the scene: per entry of the hit list (the masks after the object pass's OR)
+// the ray of shadow_ray -- P + 0.001 n from the finished record (out.hits: world normals) and the camera
+// ray, direction -light --, traced as given (raw, t_max +inf).  A ray the query's classify calls invalid is
+// not traced and leaves the pixel lit; an occluded pixel gets mark_occluded's bytes.
+template <int MODE>
+__global__ __launch_bounds__(TILE) void scene_shadow_list_kernel(LaunchParams p, const uint32_t *__restrict__ list,
+                                                                 const uint32_t *__restrict__ count, ObjectKernelArgs a) {
+    extern __shared__ uint2 stk_base[];
+    ListEntry le;
+    if (!list_entry(p, list, count, le)) return;
+    uint32_t w1 = 0, w2 = 0;
+    float nrm[3] = {0.0f, 0.0f, 0.0f}, so[3] = {0.0f, 0.0f, 0.0f}, sd[3] = {0.0f, 0.0f, 0.0f};
+    if (le.mine) {
+        primary_record(p, le.i, w1, w2, nrm);   // every entry is a hit
+        shadow_ray(p, le.x, le.gy, w2, __float_as_uint(nrm[0]), __float_as_uint(nrm[1]), __float_as_uint(nrm[2]), so, sd);
+    }
+    const float t_lim = __builtin_inff();
+    const bool live = le.mine && svo_objects::valid_ray(so, sd, t_lim);
+    if (scene_occluded<MODE>(p, a, live, so, sd, true, t_lim, stk_base + threadIdx.x)) mark_occluded(p.out, le.i, w1);
+}
+
+// The point lights over the scene: light_list_kernel with the scene-light rule (svo_scene_light.h) for the
+// origin and the facing test, and scene_occluded for the walk.  A lane's object comes out of the table by
+// selects over the eight entries (ids differ between lanes); the loop over the lights is outermost and
+// wave-uniform.  The ray {Q, 1, L} is traced with flags 0 (clamped; shading keeps L); lit iff its record
+// would have neither flag bit 0 nor bit 4.  res starts from the pixel's direct colour (black with bit 3).
+template <int MODE>
+__global__ __launch_bounds__(TILE) void scene_light_list_kernel(LaunchParams p, const uint32_t *__restrict__ list,
+                                                                const uint32_t *__restrict__ count, LightKernelArgs la,
+                                                                ObjectKernelArgs a, const uint8_t *__restrict__ ids) {
+    extern __shared__ uint2 stk_base[];
+    ListEntry le;
+    if (!list_entry(p, list, count, le)) return;
+    const bool mine = le.mine;
+    float res[3] = {0.0f, 0.0f, 0.0f}, alb[3] = {0.0f, 0.0f, 0.0f}, nrm[3] = {0.0f, 0.0f, 0.0f};
+    svo_scene_light::Face f;
+    f.Q[0] = f.Q[1] = f.Q[2] = 0.0f;
+    f.N[0] = f.N[1] = f.N[2] = 0.0f;
+    f.out = 1.0f;
+    f.g = 0;
+    f.terrain = true;
+    if (mine) {
+        float t, o[3], d[3];
+        int scale;
+        primary_colour(p, le.i, t, nrm, scale, alb, res);
+        camera_ray(p.cam, p.width, p.height, le.x, le.gy, o, d);
+        const int id = (int)ids[le.i];
+        const unsigned long long key = p.out.voxel[le.i];
+        if (id == 0 || id > a.n) {   // the terrain (an id past the table cannot come out of the object pass)
+            svo_scene_light::terrain_face(o, d, true, t, scale, key, f);
+        } else {
+            svo_objects::Object ob = a.o[0];
+#pragma unroll
+            for (int q = 1; q < svo_objects::MAX_OBJECTS; ++q)
+                if (id == q + 1) ob = a.o[q];
+            svo_scene_light::object_face(o, d, true, t, scale, key, ob, f);
+        }
+    }
+    uint2 *stk = stk_base + threadIdx.x;
+#pragma nounroll
+    for (int j = 0; j < la.n; ++j) {
+        const svo_lights::Light &l = la.l[j];   // uniform j: scalar loads
+        float L[3], d2, u;
+        bool facing, in_range;
+        svo_scene_light::toward_light(f, l.position, l.range, L, &d2, &u, &facing, &in_range);
+        const bool go = mine && facing && in_range;
+        bool lit = go;
+        if (!(l.flags & svo_lights::NO_SHADOW) && LM_OF(go) != 0) {   // wave-uniform
+            const bool live = go && svo_objects::valid_ray(f.Q, L, 1.0f);
+            lit = live && !scene_occluded<MODE>(p, a, live, f.Q, L, false, 1.0f, stk);
+        }
+        if (lit) svo_lights::add_light(res, svo_lights::light_factor(nrm, L, d2, u), l.colour, alb);
+    }
+    if (mine) store_colour(p.out, le.i, res);
 }
 
 // ------------------------------------------------------------------ skybox
@@ -3535,6 +3706,26 @@ hipError_t launch_object_rays(const QueryRay *rays, uint32_t n, const svo_object
     return hipGetLastError();
 }
 
+hipError_t launch_scene_light_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
+                                   const unsigned long long *voxel, const int32_t *object_id,
+                                   const svo_objects::Object *objects, int n_objects, const svo_lights::Light *lights,
+                                   int n_lights, QueryRay *out, hipStream_t stream) {
+    if (!rays || !hits || !voxel || !object_id || !out || !lights || n_lights < 1 || n_lights > svo_lights::MAX_LIGHTS ||
+        n_objects < 0 || n_objects > svo_objects::MAX_OBJECTS || (n_objects > 0 && !objects))
+        return hipErrorInvalidValue;
+    if (n == 0) return hipSuccess;
+    SceneLightKernelArgs a;
+    std::memset(&a, 0, sizeof a);
+    for (int j = 0; j < n_objects; ++j) a.o[j] = objects[j];
+    for (int j = 0; j < n_lights; ++j) a.l[j] = lights[j];
+    a.n_objects = n_objects;
+    a.n_lights = n_lights;
+    const size_t total = (size_t)n * (size_t)n_lights;
+    hipLaunchKernelGGL(scene_light_rays_kernel, dim3((unsigned)((total + 255u) / 256u)), dim3(256), 0, stream, rays, n, flags,
+                       hits, voxel, object_id, a, out);
+    return hipGetLastError();
+}
+
 hipError_t launch_scene_query(const LaunchParams &p, const QueryArgs &q, const svo_objects::Object *objects, int n_objects,
                               bool terrain, int32_t *object_id, int stack_mode, hipStream_t stream) {
     ObjectKernelArgs a;
@@ -3549,7 +3740,7 @@ hipError_t launch_scene_query(const LaunchParams &p, const QueryArgs &q, const s
 }
 
 hipError_t launch_objects(const LaunchParams &p, const svo_objects::Object *objects, int n_objects, int stack_mode,
-                          hipStream_t stream) {
+                          hipStream_t stream, uint8_t *ids) {
     ObjectKernelArgs a;
     if (!object_kernel_args(objects, n_objects, a) || n_objects < 1 || (!p.out.hits && !p.out.compact) || p.width <= 0 ||
         p.local_rows <= 0)
@@ -3557,8 +3748,46 @@ hipError_t launch_objects(const LaunchParams &p, const svo_objects::Object *obje
     const int bx = (p.width + 7) / 8, by = (p.local_rows + 7) / 8;
     const size_t lds = (size_t)OBJECT_SLOTS * TILE * sizeof(uint2) + lds_pad();
     const dim3 grid((unsigned)(bx * by)), block(TILE);
-    if (stack_mode == 0) hipLaunchKernelGGL((object_pass_kernel<0>), grid, block, lds, stream, p, a, p.out.hitmask, bx);
-    else hipLaunchKernelGGL((object_pass_kernel<1>), grid, block, lds, stream, p, a, p.out.hitmask, bx);
+    if (ids) {
+        if (stack_mode == 0) hipLaunchKernelGGL((object_pass_kernel<0, true>), grid, block, lds, stream, p, a, p.out.hitmask, bx, ids);
+        else hipLaunchKernelGGL((object_pass_kernel<1, true>), grid, block, lds, stream, p, a, p.out.hitmask, bx, ids);
+    } else {
+        if (stack_mode == 0) hipLaunchKernelGGL((object_pass_kernel<0, false>), grid, block, lds, stream, p, a, p.out.hitmask, bx, ids);
+        else hipLaunchKernelGGL((object_pass_kernel<1, false>), grid, block, lds, stream, p, a, p.out.hitmask, bx, ids);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_scene_shadows(const LaunchParams &p, void *scratch, const svo_objects::Object *objects, int n_objects,
+                                int stack_mode, hipStream_t stream) {
+    ObjectKernelArgs a;
+    if (!p.out.hits || !scratch || !object_kernel_args(objects, n_objects, a) || n_objects < 1 || p.width <= 0 ||
+        p.local_rows <= 0)
+        return hipErrorInvalidValue;
+    HitList h;
+    const hipError_t e = pack_hit_list(p, scratch, stream, h);
+    if (e != hipSuccess) return e;
+    const size_t lds = (size_t)OBJECT_SLOTS * TILE * sizeof(uint2) + lds_pad();
+    if (stack_mode == 0) hipLaunchKernelGGL((scene_shadow_list_kernel<0>), h.grid, dim3(TILE), lds, stream, h.q, h.list, h.cnt, a);
+    else hipLaunchKernelGGL((scene_shadow_list_kernel<1>), h.grid, dim3(TILE), lds, stream, h.q, h.list, h.cnt, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_scene_lights(const LaunchParams &p, const LightArgs &la, const svo_objects::Object *objects, int n_objects,
+                               const uint8_t *ids, int stack_mode, hipStream_t stream) {
+    LightKernelArgs l;
+    ObjectKernelArgs a;
+    if (!p.out.hits || !p.out.voxel || !la.scratch || !ids || !light_kernel_args(la.lights, la.n_lights, l) ||
+        !object_kernel_args(objects, n_objects, a) || n_objects < 1 || p.width <= 0 || p.local_rows <= 0)
+        return hipErrorInvalidValue;
+    HitList h;
+    const hipError_t e = pack_hit_list(p, la.scratch, stream, h);
+    if (e != hipSuccess) return e;
+    const size_t lds = (size_t)OBJECT_SLOTS * TILE * sizeof(uint2) + lds_pad();
+    if (stack_mode == 0)
+        hipLaunchKernelGGL((scene_light_list_kernel<0>), h.grid, dim3(TILE), lds, stream, h.q, h.list, h.cnt, l, a, ids);
+    else
+        hipLaunchKernelGGL((scene_light_list_kernel<1>), h.grid, dim3(TILE), lds, stream, h.q, h.list, h.cnt, l, a, ids);
     return hipGetLastError();
 }
 

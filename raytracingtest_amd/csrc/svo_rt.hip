@@ -273,6 +273,8 @@ struct svo_ctx {
     int max_bounces = 0;
     unsigned long long *d_refl_voxel = nullptr;
     size_t refl_voxel_cap = 0;
+    uint8_t *d_object_ids = nullptr;     // the object pass's per-pixel ids for the scene-aware light pass (grow-only)
+    size_t object_ids_cap = 0;
     // skybox (svo_set_skybox; texels null: the procedural gradient -- DESIGN.md 3.2d): the texture on this
     // device, one float4 per texel; the sky pass reads the tile hit masks from the caller's array or from
     // the head of d_shadow_list (the shadow forms' and the reflection pass's scratch)
@@ -1128,10 +1130,45 @@ int object_scratch(svo_ctx *ctx, LaunchPlan &L, svo::LaunchParams &p) {
     return SVO_OK;
 }
 
-// Behind the primary launch, before the sky pass: every pixel where a placed object is nearer.
-int object_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p) {
-    const hipError_t e = svo::launch_objects(p, ctx->objects, ctx->n_objects, L.stack_mode, L.s);
+// Behind the primary launch, before the sky pass: every pixel where a placed object is nearer.  ids: null, or
+// id_scratch's bytes for the scene-aware light pass.
+int object_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, uint8_t *ids) {
+    const hipError_t e = svo::launch_objects(p, ctx->objects, ctx->n_objects, L.stack_mode, L.s, ids);
     if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("object launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
+// The scene-aware light pass's third input: one byte per pixel, indexed as the launch's
+// outputs, shared between the streams like the other list scratch (list_scratch has called order_scratch).
+int id_scratch(svo_ctx *ctx, const svo::LaunchParams &p) {
+    const size_t px = (size_t)(p.out.frame_layout ? p.height : p.local_rows) * (size_t)p.width;
+    if (ctx->object_ids_cap < px) {
+        HIP_TRY(hipDeviceSynchronize());   // an earlier launch may still read the old ids
+        return regrow(&ctx->d_object_ids, &ctx->object_ids_cap, px, px);
+    }
+    return SVO_OK;
+}
+
+// SVO_OPT_SCENE_SHADOWS, behind the object pass: the directional shadow ray of every hit pixel of the finished
+// records, over the terrain and the objects.
+int scene_shadow_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsigned long long *caller_mask) {
+    const int rc = copy_caller_mask(ctx, L, caller_mask);
+    if (rc) return rc;
+    const hipError_t e = svo::launch_scene_shadows(p, ctx->d_shadow_list, ctx->objects, ctx->n_objects, L.stack_mode, L.s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("scene shadow launch: ") + hipGetErrorString(e));
+    return SVO_OK;
+}
+
+// ... and the point lights, with the scene-light rule and scene-wide occlusion.
+int scene_light_pass(svo_ctx *ctx, LaunchPlan &L, const svo::LaunchParams &p, unsigned long long *caller_mask) {
+    const int rc = copy_caller_mask(ctx, L, caller_mask);
+    if (rc) return rc;
+    svo::LightArgs la;
+    la.scratch = ctx->d_shadow_list;
+    la.lights = ctx->lights;
+    la.n_lights = ctx->n_lights;
+    const hipError_t e = svo::launch_scene_lights(p, la, ctx->objects, ctx->n_objects, ctx->d_object_ids, L.stack_mode, L.s);
+    if (e != hipSuccess) return fail(SVO_ERR_HIP, std::string("scene light launch: ") + hipGetErrorString(e));
     return SVO_OK;
 }
 
@@ -1611,14 +1648,16 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     if (lights_on && lod) return fail(SVO_ERR_STATE, "lights with LOD are not supported");
     if (lights_on && amb_on) return fail(SVO_ERR_STATE, "lights with an ambient term are not supported");
     // placed objects (svo_set_objects): a pass behind the primary rays that takes every pixel where an object
-    // is nearer; the other passes do not know the objects yet
+    // is nearer; of the other passes only the shadow and the light pass know the objects, and only with
+    // SVO_OPT_SCENE_SHADOWS
     const bool objects_on = ctx->n_objects > 0 && !out.fetches && !out.starts;
+    const bool scene_opt = (ctx->options & SVO_OPT_SCENE_SHADOWS) != 0;
     if (objects_on && sa) return fail(SVO_ERR_STATE, "svo_render_samples with objects is not supported");
-    if (objects_on && (ctx->options & SVO_OPT_SHADOW_RAYS))
+    if (objects_on && !scene_opt && (ctx->options & SVO_OPT_SHADOW_RAYS))
         return fail(SVO_ERR_STATE, "objects with shadow rays are not supported");
     if (objects_on && refl_on) return fail(SVO_ERR_STATE, "objects with reflection are not supported");
     if (objects_on && amb_on) return fail(SVO_ERR_STATE, "objects with an ambient term are not supported");
-    if (objects_on && lights_on) return fail(SVO_ERR_STATE, "objects with lights are not supported");
+    if (objects_on && !scene_opt && lights_on) return fail(SVO_ERR_STATE, "objects with lights are not supported");
     if (objects_on && lod) return fail(SVO_ERR_STATE, "objects with LOD are not supported");
     // skybox (svo_set_skybox): a pass behind the primary rays (and the bounces) that recolours the misses;
     // svo_render_samples blends in its own launch's epilogue, before any pass could run
@@ -1643,6 +1682,10 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     if (p.local_rows == 0) return SVO_OK;
     L.instr = out.fetches || out.starts;
     if (L.instr) p.shadows = 0;
+    // objects in shadow and light: the primary launch takes the path it takes with neither (no fused shadows,
+    // whatever shadow_form says), and both passes run behind the object pass on the finished records
+    const bool scene_shadows = objects_on && (ctx->options & SVO_OPT_SHADOW_RAYS) != 0;
+    if (scene_shadows) p.shadows = 0;
     L.s = stream ? stream : ctx->stream;
     rc = shadow_scratch(ctx, L, p);
     if (rc) return rc;
@@ -1651,8 +1694,13 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
     unsigned long long *caller_mask = nullptr;
     const bool ambient = amb_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
     const bool lights = lights_on && (p.out.rgba || p.out.rgba8 || p.out.rgb8);
-    if (reflect || ambient || lights) {   // never two of them (refused above)
+    const bool scene_lights = objects_on && lights;
+    if (reflect || ambient || lights || scene_shadows) {   // of the first three never two (refused above)
         rc = list_scratch(ctx, L, p, &caller_mask);
+        if (rc) return rc;
+    }
+    if (scene_lights) {
+        rc = id_scratch(ctx, p);
         if (rc) return rc;
     }
     if (objects_on) {   // the records change too: every launch has the pass
@@ -1699,12 +1747,20 @@ int launch(svo_ctx *ctx, int width, int height, int stack_mode, const svo_band *
         rc = ambient_pass(ctx, L, p, caller_mask);
         if (rc) return rc;
     }
-    if (lights) {
+    if (lights && !scene_lights) {
         rc = light_pass(ctx, L, p, caller_mask);
         if (rc) return rc;
     }
     if (objects_on) {
-        rc = object_pass(ctx, L, p);
+        rc = object_pass(ctx, L, p, scene_lights ? ctx->d_object_ids : nullptr);
+        if (rc) return rc;
+    }
+    if (scene_shadows) {
+        rc = scene_shadow_pass(ctx, L, p, caller_mask);
+        if (rc) return rc;
+    }
+    if (scene_lights) {
+        rc = scene_light_pass(ctx, L, p, caller_mask);
         if (rc) return rc;
     }
     if (sky) {
@@ -1966,6 +2022,7 @@ int destroy_single(svo_ctx *ctx) {
     if (ctx->d_stage) hipFree(ctx->d_stage);
     if (ctx->d_shadow_list) hipFree(ctx->d_shadow_list);
     if (ctx->d_refl_voxel) hipFree(ctx->d_refl_voxel);
+    if (ctx->d_object_ids) hipFree(ctx->d_object_ids);
     if (ctx->sky.texels) hipFree(const_cast<svo_sky::Texel *>(ctx->sky.texels));
     if (ctx->d_out_hits) hipFree(ctx->d_out_hits);
     if (ctx->d_out_rgba) hipFree(ctx->d_out_rgba);
@@ -2146,9 +2203,9 @@ int apply_config(svo_ctx *c, const svo_config &k) {
 }
 
 // ------------------------------------------------------------------ ray queries
-// The ray-batch calls (svo_trace_rays .. svo_sample_sky and their _host twins) share four pieces: HostStage
-// (the staged round trip of a _host call), on_device (the entry shell), the check_batch_* argument checks and
-// the launch-struct fillers pool_params / query_args / batch_of.  DESIGN.md 3.2i.
+// The ray-batch calls (svo_trace_rays .. svo_sample_sky, svo_scene_light_rays among them, and their _host
+// twins) share four pieces: HostStage (the staged round trip of a _host call), on_device (the entry shell), the
+// check_batch_* argument checks and the launch-struct fillers pool_params / query_args / batch_of.  DESIGN.md 3.2i.
 
 // Make stream s wait for the query-scratch work the previous user enqueued on another stream
 // (order_scratch's rule, for the query's own scratch).
@@ -2332,19 +2389,22 @@ svo::QueryArgs query_args(const svo_ray *d_rays, size_t n, uint32_t flags, const
     return q;
 }
 
-// A traced batch as the flat kernels take it (bounce, ambient, light and object rays; hits and voxel null
-// where the call has none).
+// A traced batch as the flat kernels take it (bounce, ambient, light, scene-light and object rays; hits,
+// voxel and object null where the call has none).
 struct Batch {
     const svo::QueryRay *rays;
     uint32_t n, raw;
     const svo::Hit *hits;
     const unsigned long long *voxel;
     svo::QueryRay *out;
+    const int32_t *object;   // svo_trace_scene's ids (scene-light rays only)
 };
 
-Batch batch_of(const void *d_rays, size_t n, uint32_t flags, const void *d_hits, const void *d_voxel, void *d_rays_out) {
+Batch batch_of(const void *d_rays, size_t n, uint32_t flags, const void *d_hits, const void *d_voxel, void *d_rays_out,
+               const void *d_object = nullptr) {
     return {static_cast<const svo::QueryRay *>(d_rays), (uint32_t)n, raw_bit(flags), static_cast<const svo::Hit *>(d_hits),
-            static_cast<const unsigned long long *>(d_voxel), static_cast<svo::QueryRay *>(d_rays_out)};
+            static_cast<const unsigned long long *>(d_voxel), static_cast<svo::QueryRay *>(d_rays_out),
+            static_cast<const int32_t *>(d_object)};
 }
 
 int bounce_launch(const Batch &b, hipStream_t s) {
@@ -2360,6 +2420,15 @@ int light_launch(const Batch &b, const svo_light *lights, int n_lights, hipStrea
     return launched(svo::launch_light_rays(b.rays, b.n, b.raw, b.hits, b.voxel,
                                            reinterpret_cast<const svo_lights::Light *>(lights), n_lights, b.out, s),
                     "light ray launch");
+}
+
+int scene_light_launch(const Batch &b, const svo_object *objects, int n_objects, const svo_light *lights, int n_lights,
+                       hipStream_t s) {
+    svo_objects::Object obs[svo_objects::MAX_OBJECTS] = {};
+    for (int j = 0; j < n_objects; ++j) std::memcpy(obs + j, objects + j, sizeof obs[j]);
+    return launched(svo::launch_scene_light_rays(b.rays, b.n, b.raw, b.hits, b.voxel, b.object, obs, n_objects,
+                                                 reinterpret_cast<const svo_lights::Light *>(lights), n_lights, b.out, s),
+                    "scene light ray launch");
 }
 
 int object_rays_launch(const Batch &b, const svo_object *object, hipStream_t s) {
@@ -2446,12 +2515,17 @@ int check_light_list(const svo_light *lights, int n_lights) {
     return SVO_OK;
 }
 
+// The light list of svo_light_rays and svo_scene_light_rays: a non-NULL list of 1 .. 8 valid lights.
+int check_ray_light_list(const svo_light *lights, int n_lights) {
+    if (!lights) return fail(SVO_ERR_ARG, "null light list");
+    if (n_lights < 1) return fail(SVO_ERR_ARG, "n_lights must lie in 1..8");
+    return check_light_list(lights, n_lights);
+}
+
 int check_light_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const void *hits, const void *voxel,
                      const svo_light *lights, int n_lights, const void *rays_out) {
     if (int rc = check_batch_head(ctx, rays, hits, voxel, rays_out, flags, "light-ray")) return rc;
-    if (!lights) return fail(SVO_ERR_ARG, "null light list");
-    if (n_lights < 1) return fail(SVO_ERR_ARG, "n_lights must lie in 1..8");
-    if (int rc = check_light_list(lights, n_lights)) return rc;
+    if (int rc = check_ray_light_list(lights, n_lights)) return rc;
     return check_batch_fan(rays, n, hits, voxel, (size_t)n_lights, rays_out, "light rays");
 }
 
@@ -2516,6 +2590,22 @@ int scene_device(svo_ctx *c, const svo_ray *d_rays, size_t n, int stack_mode, ui
                     "scene query launch");
 }
 
+// svo_light_rays' checks, then svo_trace_scene's for the object list (not the roots: the call reads no pool),
+// with the same complaints for the same faults; the ids are one more input the output must stay clear of.
+int check_scene_light_args(svo_ctx *ctx, const void *rays, size_t n, uint32_t flags, const void *hits, const void *voxel,
+                           const void *object, const svo_object *objects, int n_objects, const svo_light *lights,
+                           int n_lights, const void *rays_out) {
+    if (int rc = check_batch_head(ctx, rays, hits, voxel, rays_out, flags, "scene-light-ray")) return rc;
+    if (!object) return fail(SVO_ERR_ARG, "null object ids");
+    if (n_objects > 0 && !objects) return fail(SVO_ERR_ARG, "null object list");
+    if (int rc = check_object_list(objects, n_objects)) return rc;
+    if (int rc = check_ray_light_list(lights, n_lights)) return rc;
+    if (int rc = check_batch_fan(rays, n, hits, voxel, (size_t)n_lights, rays_out, "light rays")) return rc;
+    if (ranges_overlap(rays_out, 32 * n * (size_t)n_lights, object, 4 * n))
+        return fail(SVO_ERR_ARG, "the output ray list overlaps an input");
+    return SVO_OK;
+}
+
 int check_sky_args(svo_ctx *ctx, const float *dirs, size_t n, const float *rgba) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
     if (!dirs) return fail(SVO_ERR_ARG, "null direction list");
@@ -2529,21 +2619,23 @@ int sky_launch(svo_ctx *c, const void *d_dirs, size_t n, void *d_rgba, hipStream
                                            static_cast<float4 *>(d_rgba), s), "sky sample launch");
 }
 
-// The host twin of a call on a traced batch (hits, voxel null where the call has none): the inputs staged,
-// launch(batch, s), and n * fan rays brought back -- fan 0: n rays, written over the staged input.
+// The host twin of a call on a traced batch (hits, voxel, object null where the call has none): the inputs
+// staged, launch(batch, s), and n * fan rays brought back -- fan 0: n rays, written over the staged input.
 template <class F>
 int batch_host(svo_ctx *ctx, const char *name, const void *rays, size_t n, uint32_t flags, const void *hits,
-               const void *voxel, size_t fan, void *rays_out, F &&launch) {
+               const void *voxel, size_t fan, void *rays_out, F &&launch, const int32_t *object = nullptr) {
     return on_device(ctx, name, nullptr, false, [&](svo_ctx *c, hipStream_t s) {
         HostStage st(c);
         const size_t out_bytes = 32 * n * std::max<size_t>(fan, 1);
         const size_t p_rays = st.part(32 * n), p_hits = st.part(hits ? 24 * n : 0), p_vox = st.part(voxel ? 8 * n : 0),
-                     p_out = fan ? st.part(out_bytes) : p_rays;
+                     p_id = st.part(object ? 4 * n : 0), p_out = fan ? st.part(out_bytes) : p_rays;
         if (int rc = st.begin()) return rc;
         if (int rc = st.upload(p_rays, rays, 32 * n)) return rc;
         if (int rc = st.upload(p_hits, hits, 24 * n)) return rc;
         if (int rc = st.upload(p_vox, voxel, 8 * n)) return rc;
-        if (int rc = launch(batch_of(st.at(p_rays), n, flags, st.at_if(hits, p_hits), st.at_if(voxel, p_vox), st.at(p_out)), s))
+        if (int rc = st.upload(p_id, object, 4 * n)) return rc;
+        if (int rc = launch(batch_of(st.at(p_rays), n, flags, st.at_if(hits, p_hits), st.at_if(voxel, p_vox), st.at(p_out),
+                                     st.at_if(object, p_id)), s))
             return rc;
         if (int rc = st.download(rays_out, p_out, out_bytes)) return rc;
         return st.finish();
@@ -2663,6 +2755,32 @@ int svo_light_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t fl
     if (n == 0) return SVO_OK;
     return batch_host(ctx, "svo_light_rays_host", rays, n, flags, hits, voxel, (size_t)n_lights, rays_out,
                       [&](const Batch &b, hipStream_t s) { return light_launch(b, lights, n_lights, s); });
+}
+
+int svo_scene_light_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_hit *d_hits,
+                         const uint64_t *d_voxel, const int32_t *d_object, const svo_object *objects, int n_objects,
+                         const svo_light *lights, int n_lights, svo_ray *d_rays_out, void *stream) {
+    if (int rc = check_scene_light_args(ctx, d_rays, n, flags, d_hits, d_voxel, d_object, objects, n_objects, lights, n_lights,
+                                        d_rays_out))
+        return rc;
+    if (int rc = check_batch_alignment(d_rays, d_rays_out, d_hits, d_voxel)) return rc;
+    if ((uintptr_t)d_object & 3u) return fail(SVO_ERR_ARG, "object ids must be 4-byte aligned");
+    if (n == 0) return SVO_OK;
+    return on_device(ctx, "svo_scene_light_rays", stream, false, [&](svo_ctx *, hipStream_t s) {
+        return scene_light_launch(batch_of(d_rays, n, flags, d_hits, d_voxel, d_rays_out, d_object), objects, n_objects, lights,
+                                  n_lights, s);
+    });
+}
+
+int svo_scene_light_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint32_t flags, const svo_hit *hits,
+                              const uint64_t *voxel, const int32_t *object, const svo_object *objects, int n_objects,
+                              const svo_light *lights, int n_lights, svo_ray *rays_out) {
+    if (int rc = check_scene_light_args(ctx, rays, n, flags, hits, voxel, object, objects, n_objects, lights, n_lights, rays_out))
+        return rc;
+    if (n == 0) return SVO_OK;
+    return batch_host(ctx, "svo_scene_light_rays_host", rays, n, flags, hits, voxel, (size_t)n_lights, rays_out,
+                      [&](const Batch &b, hipStream_t s) { return scene_light_launch(b, objects, n_objects, lights, n_lights, s); },
+                      object);
 }
 
 int svo_object_rays(svo_ctx *ctx, const svo_ray *d_rays, size_t n, uint32_t flags, const svo_object *object,
@@ -3495,7 +3613,8 @@ int svo_count_fetches(svo_ctx *ctx, int width, int height, int stack_mode, const
 
 int svo_set_options(svo_ctx *ctx, uint32_t options) {
     if (!ctx) return fail(SVO_ERR_ARG, "null context");
-    if (options & ~(uint32_t)(SVO_OPT_SHADOW_RAYS | SVO_OPT_KERNEL_TIMING | SVO_OPT_COUNT_BEAM)) return fail(SVO_ERR_ARG, "unknown option bits");
+    if (options & ~(uint32_t)(SVO_OPT_SHADOW_RAYS | SVO_OPT_KERNEL_TIMING | SVO_OPT_COUNT_BEAM | SVO_OPT_SCENE_SHADOWS))
+        return fail(SVO_ERR_ARG, "unknown option bits");
     for (svo_ctx *m : ctx->members) m->options = options;
     ctx->options = options;
     return SVO_OK;

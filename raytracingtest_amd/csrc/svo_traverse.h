@@ -377,11 +377,30 @@ hipError_t launch_object_rays(const QueryRay *rays, uint32_t n, const svo_object
 // 0 terrain, j + 1 object j).
 hipError_t launch_scene_query(const LaunchParams &p, const QueryArgs &q, const svo_objects::Object *objects, int n_objects,
                               bool terrain, int32_t *object_id, int stack_mode, hipStream_t stream);
+// svo_scene_light_rays: out[i * n_lights + j] = the world-space shadow ray (svo_scene_light.h) of the scene
+// hit rays[i], hits[i] / voxel[i] / object_id[i] toward lights[j], or the dead ray.  objects (0 .. 8) and
+// lights (1 .. 8) are host arrays that travel as a kernel argument.  flags: QUERY_RAW.  A flat launch, one
+// thread per output entry; out must not overlap the inputs.  Reads no pool.
+hipError_t launch_scene_light_rays(const QueryRay *rays, uint32_t n, uint32_t flags, const Hit *hits,
+                                   const unsigned long long *voxel, const int32_t *object_id,
+                                   const svo_objects::Object *objects, int n_objects, const svo_lights::Light *lights,
+                                   int n_lights, QueryRay *out, hipStream_t stream);
 // Object pass behind a render launch's primary rays (object_pass_kernel): one wave64 per 8x8 tile of the
 // launch's rows.  p: the launch's own parameters; out.hits or out.compact hold the primary records, and a
 // pixel where an object is nearer gets every non-null output rewritten and its bit set in out.hitmask
 // (nullable).  n_objects 1 .. 8.
+// ids (nullable): per pixel of the launch's rows, indexed as its outputs, 0 where the primary record stood and
+// j + 1 where object j took the pixel.
 hipError_t launch_objects(const LaunchParams &p, const svo_objects::Object *objects, int n_objects, int stack_mode,
-                          hipStream_t stream);
+                          hipStream_t stream, uint8_t *ids = nullptr);
+// SVO_OPT_SCENE_SHADOWS, behind the object pass, in the list-pass frame (scratch:
+// shadow_list_bytes, its head the launch's hit masks after the object pass).  Both need out.hits (world
+// normals).  launch_scene_shadows: the directional shadow ray of every hit pixel over the terrain and the
+// objects; an occluded pixel gets flag bit 3 and a black Result in every output.  launch_scene_lights: the
+// point lights with the scene-light rule and scene-wide occlusion; needs out.voxel and the object pass's ids.
+hipError_t launch_scene_shadows(const LaunchParams &p, void *scratch, const svo_objects::Object *objects, int n_objects,
+                                int stack_mode, hipStream_t stream);
+hipError_t launch_scene_lights(const LaunchParams &p, const LightArgs &la, const svo_objects::Object *objects, int n_objects,
+                               const uint8_t *ids, int stack_mode, hipStream_t stream);
 
 }  // namespace svo

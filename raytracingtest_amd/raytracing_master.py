@@ -149,6 +149,13 @@ class RaytracingMaster:
         reference's commented-out test, RaytraceCompute.compute:105-112)."""
         self._set_option(_lib.SVO_OPT_SHADOW_RAYS, enable)
 
+    def SetSceneShadows(self, enable=True):
+        """Let the shadow pass (SetShadowRays) and the light pass (SetLights) of a render know the placed
+        objects (SetObjects): objects cast and receive shadows (SVO_OPT_SCENE_SHADOWS; scene_light.py is the
+        rule).  Off by default: a render with objects then refuses shadow rays and lights.  Without objects
+        the option changes nothing."""
+        self._set_option(_lib.SVO_OPT_SCENE_SHADOWS, enable)
+
     def SetLod(self, ray_size_coef, ray_size_bias=0.0):
         """Level-of-detail termination of the primary rays (svo_set_lod; Laine-Karras's test, commented
         out at NVIDIASVO.compute:77-79): a voxel whose side is at most tc_max * ray_size_coef +
@@ -663,6 +670,41 @@ class RaytracingMaster:
         check(_lib.lib().svo_trace_scene(self._ctx, rays_ptr, int(n), stack_mode, flags,
                                          rec.ctypes.data if len(rec) else None, len(rec), ctypes.byref(out), object_id,
                                          stream), "svo_trace_scene")
+
+    def SceneLightRays(self, rays, hits, voxel, object_id, objects, lights, raw=False):
+        """The world-space shadow rays of a scene query's hits toward each light (svo_scene_light_rays_host;
+        scene_light.scene_light_rays is its numpy statement): rays as given to TraceScene, its hit records,
+        voxel keys and object ids, and the objects it was traced with; raw: whether it was traced with
+        raw=True.  Returns RAY_DTYPE [n * n_lights], entry i * n_lights + j = the ray of hit i toward lights[j]
+        with t_max 1 (the light itself): a dead ray where there was no hit, or the light lies behind the
+        entered face or out of range."""
+        from .lights import make_lights
+        from .objects import make_objects
+        rays, hits, voxel = batch_arrays(rays, hits, voxel)
+        ids = np.ascontiguousarray(object_id, np.int32).reshape(-1)
+        if len(ids) != len(rays):
+            raise ValueError(f"{len(rays)} rays, {len(ids)} object ids")
+        obs = make_objects(objects if objects is not None else [])
+        rec = make_lights(lights)
+        out = np.zeros(len(rays) * len(rec), _lib.RAY_DTYPE)
+        check(_lib.lib().svo_scene_light_rays_host(self._ctx, rays.ctypes.data, len(rays), self._query_flags(False, raw),
+                                                   hits.ctypes.data, voxel.ctypes.data, ids.ctypes.data,
+                                                   obs.ctypes.data if len(obs) else None, len(obs), rec.ctypes.data,
+                                                   len(rec), out.ctypes.data), "svo_scene_light_rays_host")
+        return out
+
+    def scene_light_rays_device(self, rays_ptr, n, hits, voxel, object_id, out, objects, lights, raw=False, stream=None):
+        """Asynchronous svo_scene_light_rays on device buffers: rays_ptr = n svo_ray records, out = n * n_lights
+        (16-byte aligned, no overlap with the inputs), hits (n x 24 bytes), voxel (n uint64) and object_id (n
+        int32) the results of the batch's trace_scene_device; objects, lights: host records (the call copies
+        them before it returns)."""
+        from .lights import make_lights
+        from .objects import make_objects
+        obs = make_objects(objects if objects is not None else [])
+        rec = make_lights(lights)
+        check(_lib.lib().svo_scene_light_rays(self._ctx, rays_ptr, int(n), self._query_flags(False, raw), hits, voxel,
+                                              object_id, obs.ctypes.data if len(obs) else None, len(obs),
+                                              rec.ctypes.data, len(rec), out, stream), "svo_scene_light_rays")
 
     def beam_starts_device(self, width, height, starts_ptr, band=None, stream=None):
         """svo_beam_starts: every primary ray's beam start (SVO-space t, -inf: the cube entry) into a

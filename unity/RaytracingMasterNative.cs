@@ -154,6 +154,20 @@ public static class SvoNative {
                                                                    uint flags, [In] SvoObject[] objects, int nObjects,
                                                                    [Out] SvoHit[] hits, [Out] Vector4[] position,
                                                                    [Out] ulong[] voxel, [Out] int[] objectId);
+    // Render options (svo_rt.h svo_set_options): the directional light's shadow rays, and the shadow and light passes
+    // that know the placed objects
+    public const uint OptShadowRays = 1, OptSceneShadows = 8;
+    [DllImport(Lib)] public static extern int svo_set_options(IntPtr ctx, uint options);
+    // Objects in light (svo_rt.h): svo_light_rays for the results of svo_trace_scene, world-space shadow rays
+    [DllImport(Lib)] public static extern int svo_scene_light_rays(IntPtr ctx, IntPtr dRays, UIntPtr n, uint flags, IntPtr dHits,
+                                                                   IntPtr dVoxel, IntPtr dObject, [In] SvoObject[] objects,
+                                                                   int nObjects, [In] SvoLight[] lights, int nLights,
+                                                                   IntPtr dRaysOut, IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_scene_light_rays_host(IntPtr ctx, [In] SvoRay[] rays, UIntPtr n, uint flags,
+                                                                        [In] SvoHit[] hits, [In] ulong[] voxel,
+                                                                        [In] int[] objectId, [In] SvoObject[] objects,
+                                                                        int nObjects, [In] SvoLight[] lights, int nLights,
+                                                                        [Out] SvoRay[] raysOut);
     // Skybox (svo_rt.h): the reference's _SkyboxTexture for rays that leave the scene, and its rule for ray queries
     public const uint SkyBilinear = 1, SkyClampV = 2;
     [DllImport(Lib)] public static extern int svo_set_skybox(IntPtr ctx, [In] Color[] rgba, int width, int height, uint flags);
@@ -259,6 +273,12 @@ public class RaytracingMasterNative : MonoBehaviour {
     public bool skyboxClampV;                    // wrapModeV Clamp (false: Repeat, Unity's import default)
     public enum ShadowForm { Fused = 0, TilePass = 1, CompactedList = 2 }
     public ShadowForm shadowForm = ShadowForm.Fused;
+    // Shadow rays toward the directional light (SVO_OPT_SHADOW_RAYS; it changes the image), and beside it the
+    // switch that lets shadow rays and point lights see the placed objects (SVO_OPT_SCENE_SHADOWS): objects then
+    // cast and receive shadows, every shadow ray may walk up to eight more cubes, and without it a render with
+    // placed objects refuses shadow rays and lights.
+    public bool shadowRays;
+    public bool sceneShadows;
 
     IntPtr _ctx;
     Camera _camera;
@@ -359,6 +379,8 @@ public class RaytracingMasterNative : MonoBehaviour {
         cfg.moveEvery = moveEvery;
         cfg.shadowForm = (int)shadowForm;
         SvoNative.Check(SvoNative.svo_set_config(_ctx, ref cfg), "svo_set_config");
+        uint options = (shadowRays ? SvoNative.OptShadowRays : 0u) | (sceneShadows ? SvoNative.OptSceneShadows : 0u);
+        SvoNative.Check(SvoNative.svo_set_options(_ctx, options), "svo_set_options");
     }
 
     void OnValidate() { ApplyConfig(); }   // an Inspector edit at run time takes effect at the next frame
@@ -540,8 +562,8 @@ public class RaytracingMasterNative : MonoBehaviour {
     public PlacedObject[] placedObjects;
 
     // The placed objects of the renders (svo_set_objects; it changes the image): up to 8.  Call it whenever one
-    // moves; null or an empty array turns them off.  Not supported together with shadow rays, specular,
-    // lodPixels, ambient, lights or gpus > 1.
+    // moves; null or an empty array turns them off.  Shadow rays and lights need sceneShadows
+    // with them; not supported together with specular, lodPixels, ambient or gpus > 1.
     public void SetObjects(PlacedObject[] objects) {
         int n = objects == null ? 0 : Mathf.Min(objects.Length, SvoNative.MaxObjects);
         var rec = new SvoNative.SvoObject[n];
