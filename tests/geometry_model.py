@@ -287,10 +287,13 @@ def _gap(tn, tf, d):
     return g
 
 
-def _crossings(lo, hi, size, o, d, m, gap=False):
+def _crossings(lo, hi, size, o, d, m, gap=False, t_lim=None):
     """Grown and shrunk crossings of every (ray, leaf): dict of [R, L] arrays.  may, entry_g: the grown
     box (entry clamped at 0, inf off the ray); entry_s, exit_s: the shrunk box; must[mode]; entry_true:
-    the box's own slab entry (clamped at 0); axis_d: |d| of the axis it enters through."""
+    the box's own slab entry (clamped at 0); axis_d: |d| of the axis it enters through.  t_lim [R]: the
+    rays end there -- a leaf is a may leaf only if its grown crossing begins inside [0, t_lim], a must leaf
+    only if its shrunk crossing has a positive length inside it (the stack-rounding condition of the HLSL
+    mode stays one on the whole crossing: it is about what the walk descends into, not about the filter)."""
     o, d, m3 = o[:, None, :], d[:, None, :], m[:, None, None]
     tn, tf, mt = _slabs(lo, hi, o, d, m3)
     par = np.broadcast_to(d == 0.0, tn.shape)
@@ -313,7 +316,15 @@ def _crossings(lo, hi, size, o, d, m, gap=False):
         cross = np.where((size > 2.0 * m[:, None]) & np.isfinite(tx_s - entry_s), tx_s - entry_s, -np.inf)
     k = tn_g.argmax(axis=2)
     extra = {"gap": _gap(tn, tf, d)} if gap else {}
-    return {**extra, "may": may, "must": {EXACT: cross > 0.0, HLSL: cross > slack}, "entry_g": entry_g, "entry_s": entry_s,
+    must = {EXACT: cross > 0.0, HLSL: cross > slack}
+    if t_lim is not None:
+        tl = np.asarray(t_lim, np.float64)[:, None]
+        may = may & (np.maximum(te_g, 0.0) <= tl)
+        entry_g = np.where(may, entry_g, np.inf)
+        with np.errstate(invalid="ignore"):
+            inside = np.minimum(tx_s, tl) - entry_s > 0.0
+        must = {mode: v & inside for mode, v in must.items()}
+    return {**extra, "may": may, "must": must, "entry_g": entry_g, "entry_s": entry_s, "exit_s": tx_s,
             "entry_true": np.maximum(tn_g.max(axis=2), 0.0), "slack": slack,
             "axis_d": np.take_along_axis(np.broadcast_to(np.abs(d), tn_g.shape), k[..., None], axis=2)[..., 0]}
 
@@ -333,20 +344,23 @@ def _summarise(c, mode, index=None):
     col = (lambda a: a) if index is None else (lambda a: index[a])
     return {"n_may": n_may, "n_must": n_must, "first": np.where(n_may > 0, col(first), -1), "decided": decided,
             "must_entry": entry_s[r, fm], "must_slack": np.where(n_must > 0, slack, 0.0),
-            "first_must": np.where(n_must > 0, col(fm), -1)}
+            "first_must": np.where(n_must > 0, col(fm), -1),
+            # for a union of several pools' sets (tests/scene_geometry_model.py): the earliest may leaf's grown
+            # entry, whether it is a must leaf and where its shrunk crossing begins, and the next grown entry
+            "first_entry": c["entry_g"][r, first], "first_is_must": must[r, first] & (n_may > 0),
+            "first_entry_s": entry_s[r, first], "other_entry": others.min(axis=1)}
 
 
 def _no_leaf(n):
     z = np.zeros(n)
     return {"n_may": z.astype(np.int64), "n_must": z.astype(np.int64), "first": z.astype(np.int64) - 1,
-            "decided": z.astype(bool), "must_entry": z + np.inf, "must_slack": z, "first_must": z.astype(np.int64) - 1}
+            "decided": z.astype(bool), "must_entry": z + np.inf, "must_slack": z.copy(), "first_must": z.astype(np.int64) - 1,
+            "first_entry": z + np.inf, "first_is_must": z.astype(bool), "first_entry_s": z + np.inf, "other_entry": z + np.inf}
 
 
-@functools.lru_cache(maxsize=None)
-def _cells(name):
+def cells_of(leaves):
     """Leaves grouped by the cell of their ancestor three levels up (at most level 4) -- a cull, a superset
     of every may set: order, offsets, cell boxes."""
-    _, leaves = pool(name)
     level = int(min(4, leaves[:, 2].min() - 3))
     c = leaves[:, 3:6] >> (leaves[:, 2] - level)[:, None]
     key = (c[:, 0] << 8) | (c[:, 1] << 4) | c[:, 2]
@@ -357,20 +371,41 @@ def _cells(name):
     return order, np.append(start, len(order)), clo, clo + 2.0 ** -level
 
 
+@functools.lru_cache(maxsize=None)
+def _cells(name):
+    return cells_of(pool(name)[1])
+
+
 def model(name, traced):
-    """Per-ray sets of the rays as traced on a pool: {stack mode: dict of [n] arrays} with n_may, n_must,
+    """model_of on a named pool for rays as traced (sanitize_rays output), the margin derived from the rays."""
+    return model_of(pool(name)[1], _cells(name), *svo_rays(traced))
+
+
+def model_of(leaves, cells, o, d, m, t_lim=None, skip=None):
+    """Per-ray sets of rays on a leaf table: {stack mode: dict of [n] arrays} with n_may, n_must,
     first (earliest may leaf row, -1), decided (that leaf is the answer whatever the rounding),
     first_must (row, -1), must_entry (shrunk entry of the earliest must leaf, inf) and must_slack (its
-    HLSL slack)."""
-    _, leaves = pool(name)
+    HLSL slack).  leaves: SVOData.leaf_voxels() rows; cells: cells_of(leaves); o, d [n, 3] float64: the rays in
+    the table's SVO frame; m [n]: their margins; t_lim [n]: the parameter interval's end (None: unbounded);
+    skip [n]: a leaf row per ray that is left out of its sets (-1: none)."""
     lo, hi, size = boxes(leaves)
-    o, d, m = svo_rays(traced)
     n = len(o)
-    order, offs, clo, chi = _cells(name)
+    order, offs, clo, chi = cells
     inf = np.full((1, len(clo)), np.inf)
-    touched = np.concatenate([_crossings(clo[None], chi[None], inf, o[s:s + 512], d[s:s + 512], m[s:s + 512])["may"]
-                              for s in range(0, n, 512)]) if n else np.zeros((0, len(clo)), bool)
+    lim = (lambda sl: None) if t_lim is None else (lambda sl: np.asarray(t_lim, np.float64)[sl])
+    touched = np.concatenate([_crossings(clo[None], chi[None], inf, o[s:s + 512], d[s:s + 512], m[s:s + 512],
+                                         t_lim=lim(slice(s, s + 512)))["may"]
+                              for s in range(0, n, 512)]) if n and len(clo) else np.zeros((n, len(clo)), bool)
     out = {mode: _no_leaf(n) for mode in (EXACT, HLSL)}
+
+    def crossings(idx, e):
+        c = _crossings(lo[None, idx], hi[None, idx], size[None, idx], o[e], d[e], m[e], t_lim=lim(e))
+        if skip is not None:
+            own = idx[None, :] == np.asarray(skip)[e][:, None]
+            c["may"] = c["may"] & ~own
+            c["entry_g"] = np.where(own, np.inf, c["entry_g"])
+            c["must"] = {mode: v & ~own for mode, v in c["must"].items()}
+        return c
 
     def put(rows, c, index=None):
         for mode in (EXACT, HLSL):
@@ -382,21 +417,24 @@ def model(name, traced):
         for s in range(0, len(live), 256):       # neighbours in a frame touch the same few cells
             e = live[s:s + 256]
             idx = np.concatenate([order[offs[c]:offs[c + 1]] for c in np.flatnonzero(touched[e].any(axis=0))])
-            put(e, _crossings(lo[None, idx], hi[None, idx], size[None, idx], o[e], d[e], m[e]), idx)
+            put(e, crossings(idx, e), idx)
     else:
         for i in live:
             idx = np.concatenate([order[offs[c]:offs[c + 1]] for c in np.flatnonzero(touched[i])])
             j = slice(i, i + 1)
-            put(j, _crossings(lo[None, idx], hi[None, idx], size[None, idx], o[j], d[j], m[j]), idx)
+            put(j, crossings(idx, j), idx)
     return out
 
 
 def pairs(name, traced, rows):
+    """pairs_of on a named pool for rays as traced."""
+    return pairs_of(pool(name)[1], rows, *svo_rays(traced))
+
+
+def pairs_of(leaves, rows, o, d, m, t_lim=None):
     """The crossing of ray i with leaf rows[i] alone: _crossings' arrays as [n]."""
-    _, leaves = pool(name)
     lo, hi, size = boxes(leaves[rows])
-    o, d, m = svo_rays(traced)
-    c = _crossings(lo[:, None], hi[:, None], size[:, None], o, d, m, gap=True)
+    c = _crossings(lo[:, None], hi[:, None], size[:, None], o, d, m, gap=True, t_lim=t_lim)
     return {k: v[:, 0] for k, v in c.items() if isinstance(v, np.ndarray)}
 
 
@@ -417,26 +455,37 @@ def decided_share(summaries):
 
 
 def leaf_rows(name, hits):
-    """Leaf row of every hit record (parent, hit_idx); AssertionError if one is no leaf of the pool."""
-    _, leaves = pool(name)
+    """leaf_rows_of on a named pool (uploaded at descriptor 0)."""
+    return leaf_rows_of(pool(name)[1], hits)
+
+
+def leaf_rows_of(leaves, hits, root=0):
+    """Leaf row of every hit record (parent - root, hit_idx); AssertionError if one is no leaf of the pool."""
     code = leaves[:, 0] * 8 + leaves[:, 1]
     srt = np.argsort(code)
-    want = hits["parent"].astype(np.int64) * 8 + hits["hit_idx"]
+    want = (hits["parent"].astype(np.int64) - int(root)) * 8 + hits["hit_idx"]
+    if not len(code):
+        assert not len(want), "a reported voxel in an empty pool"
+        return np.zeros(0, np.int64)
     pos = np.clip(np.searchsorted(code[srt], want), 0, len(code) - 1)
     bad = code[srt][pos] != want
     assert not bad.any(), f"{bad.sum()} reported voxels are no leaf of the pool, first (parent, slot) " \
-                          f"{(int(hits['parent'][bad][0]), int(hits['hit_idx'][bad][0]))}"
+                          f"{(int(hits['parent'][bad][0]) - int(root), int(hits['hit_idx'][bad][0]))}"
     return srt[pos]
 
 
 # ---------------------------------------------------------------------------------- assertions
 def check(name, traced, mode, summary, hits, voxel, what=""):
+    """check_of on a named pool for rays as traced."""
+    return check_of(pool(name)[1], *svo_rays(traced), mode, summary, hits, voxel, what=what)
+
+
+def check_of(leaves, o, d, m, mode, summary, hits, voxel, what=""):
     """Section-2 assertions on any tracer's hit records and voxel keys.  Returns the figures for the
     record: rays, hits, decided share, max_gap_ulp -- the largest distance of a reported voxel from the
     float64 ray in units of 2^-23 (the margin allows K max(1, |o'|_inf) of them) -- and max_entry_dev,
-    the largest deviation of t from the leaf's entry in units of 2^-23 max(1, |o'|_inf) / min |d_k| (K allowed)."""
-    _, leaves = pool(name)
-    o, d, m = svo_rays(traced)
+    the largest deviation of t from the leaf's entry in units of 2^-23 max(1, |o'|_inf) / min |d_k| (K allowed).
+    leaves, o, d, m: as model_of takes them."""
     voxel = np.asarray(voxel, np.uint64)
     flags = hits["flags"]
     assert not np.any(flags & (FLAG_CAP | FLAG_OVERFLOW)), f"{what}: iteration-cap or overflow flag"
@@ -445,10 +494,10 @@ def check(name, traced, mode, summary, hits, voxel, what=""):
     assert np.array_equal(hit, hits["parent"] != 0xFFFFFFFF), f"{what}: hit bit and parent disagree"
     h = np.flatnonzero(hit)
     try:
-        rows = leaf_rows(name, hits[h])
+        rows = leaf_rows_of(leaves, hits[h])
     except AssertionError as e:
         raise AssertionError(f"{what}: {e}") from None
-    p = pairs(name, traced[h], rows)
+    p = pairs_of(leaves, rows, o[h], d[h], m[h])
     assert p["may"].all(), f"{what}: {np.count_nonzero(~p['may'])} reported voxels off the ray, first rays {h[~p['may']][:5]}"
     assert np.array_equal(hits["hit_scale"][h], 23 - leaves[rows, 2]), f"{what}: hit_scale != 23 - L"
     assert np.array_equal(voxel[h], voxel_keys(leaves[rows])), f"{what}: voxel key"

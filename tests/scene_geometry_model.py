@@ -1,0 +1,763 @@
+"""Float64 world geometry of a scene -- a terrain plus up to 8 placed pools -- with a margin for what the f32
+object transform and the f32 walk may get wrong: the reference of tests/test_scene_geometry_model.py and
+tests/test_gpu_scene_geometry.py.  Plain numpy on top of tests/geometry_model.py; it calls neither the oracle,
+the library, objects.py nor scene_light.py (only the builders, for the pools, and object_util.rot for the
+committed rotations).
+
+Truth
+-----
+A placed pool's voxels are where include/svo_rt.h says they are: the object frame is the world convention's
+[-16, 16]^3 cube, mapped by x_w = p + 2^k R x_o with R the float32 table entries read as float64 and k the
+record's scale_log2.  For candidate c (0 the terrain, j + 1 object j) the world ray (o, d) is taken into the
+candidate's frame with the exact inverse of that map, in float64:
+
+    x_o = 2^-k inv(R) (o - p),   d' = 2^-k inv(R) d,   o' = x_o / 32 + 1.5
+
+(np.linalg.inv(R), not R^T: the table is orthonormal only to 2^-10).  The terrain is the identity map.  The
+parameter is shared between the frames -- origin and direction take the same scale -- so a record's t / 2048
+is the SVO parameter in every frame, and t_max / 32 ends the ray in every frame.
+
+Margin (u = 2^-24; nothing here is fitted to a tracer's output)
+----------------------------------------------------------------
+Per ray i and candidate c
+
+    m_ic = K * 2^-23 * max(1, |o'|_inf) + e_o + T * e_d
+
+K = 10 is geometry_model's: the walk's own error on the ray it is given (the + 1.5, coef, bias, the plane
+compares).  e_o and e_d bound what the f32 object_ray (csrc/svo_object.h, step 2 of the object rule) does to
+the ray before the walk sees it, against the float64 transform above.  The header computes, every operation
+one rounding,
+
+    q = o - p                                           1 rounding: |dq_i| <= u |q_i|
+    o'_j = ((R_0j q_0 + R_1j q_1) + R_2j q_2) s          3 products, 2 sums; s = 2^-k exact
+
+A term of the sum passes through at most 3 roundings (its product and two sums), so with the rounding of q
+the computed value is sum_i R_ij q_i (1 + th_i), |th_i| <= 4u to first order:
+
+    |o'_j(f32) - s (R^T q)_j| <= 4u s sum_i |R_ij| |q_i|
+
+and the float64 truth uses inv(R) where the header uses R^T, a further s |((R^T - inv(R)) q)_j|.  In SVO
+units (the / 32 of the walk's own transform is exact):
+
+    e_o = (4u s max_j sum_i |R_ij| |q_i| + s |(R^T - inv(R)) q|_inf) / 32
+
+The direction has no subtraction before it, 3 roundings per term:
+
+    e_d = 3u s max_j sum_i |R_ij| |d_i| + s |(R^T - inv(R)) d|_inf
+
+A direction error displaces the point at parameter t by t e_d; the walk looks at no point behind the exit of
+the object's cube, so T is the float64 SVO-parameter exit of the cube [1, 2]^3 in the candidate's frame (for
+a ray that misses the cube, the later of its slab entry and exit: the parameter at which it passes the cube,
+and the larger one).  For the terrain e_o = e_d = 0 and the margin is geometry_model's.  Second-order terms:
+those of e_o are below 10 u^2 s |q| / 32 <= 10 u^2 (|o'|_inf + 1.5) and those of T e_d below
+6 u^2 T |d'| <= 6 u^2 (|o'|_inf + 2) sqrt(3); together less than 2^-40 max(1, |o'|_inf), which the
+0.5 * 2^-23 max(1, |o'|_inf) that K = 10 leaves over the derived 9.5 covers as it covers the walk's own.
+
+The entry-distance assertion keeps geometry_model's form, |t / 2048 - entry| <= m_ic / min_k |d'_k|: a plane
+moved by m moves t by m / |d'_k|, and the relative error e_d / |d'_k| of the computed d'_k moves t by
+t e_d / |d'_k| <= T e_d / |d'_k|, which m_ic contains.
+
+Scene sets
+----------
+The union over the candidates of geometry_model's may and must sets, each taken in its candidate's frame
+with its candidate's margin, entries in the shared parameter.  A ray is scene-decided when its earliest may
+leaf over all candidates (by grown entry) is a must leaf and no other may leaf of any candidate enters
+(grown) before that leaf's shrunk entry.  Ties at equal t (the earlier candidate wins) are a convention, not
+geometry: a tie is never decided here and stays pinned by the byte tests of tests/test_objects.py.  The cube
+test and the entry skip `t_entry < best.t` of the rule are no part of the truth: a ray's answer is the
+nearest voxel of the union, whatever order the candidates are walked in.
+
+Position output: hit_position adds 32 t d to the SVO origin (the reference's quirk, NVIDIASVO.compute:163)
+and clamps the result into the voxel, so the output is a point of the reported voxel and in general not the
+point o + (t / 64) d: no tolerance against that point can be derived, and the box condition stands alone.
+The clamp and the final (c - 1.5) * 64 are exact in f32 (c in [1, 2]), so the output, taken to the world by
+p + 2^k R (pos / 2) and back into the frame by the float64 inverse, must lie in the leaf's box grown by the
+margin (the round trip's own float64 error is far below it).
+"""
+import functools
+
+import numpy as np
+
+from raytracingtest_amd.builder import build_from_leaves
+from raytracingtest_amd.camera import Camera, look_rotation
+from raytracingtest_amd.query import camera_rays, make_rays, sanitize_rays
+from tests import geometry_model as gm
+from tests.geometry_model import EXACT, HLSL, K, ULP
+from tests.object_util import axis_rotations, rot
+
+U = 2.0 ** -24
+MIN_DIR = 2.0 ** -22
+CAM_W, CAM_H = 128, 96
+CAM_SIZES = {"camera": (CAM_W, CAM_H), "camera_small": (61, 45)}      # the second one lies off the 8 x 8 tile grid
+N_RAYS = 1000
+FAMILIES = ("far", "inside", "between", "tmax", "camera", "camera_small")
+LIGHT = (0.35, -0.85, 0.4, 1.0)          # the directional light of the shadow renders: from above the floor
+DECIDED_FLOOR = 0.95
+
+
+# --------------------------------------------------------------------------------------- pools
+def _terrain_leaves():
+    """Depth 6 (half-unit voxels): a floor two voxels thick (iy 20, 21: world y in [-6, -5]) over x, z in
+    [4, 60), six random-walk clusters above it, and a 3-unit slab at world y = 9 that shades one side of the
+    scene set's sphere."""
+    g = np.arange(4, 60)
+    x, z = np.meshgrid(g, g, indexing="ij")
+    floor = np.concatenate([np.stack([x.ravel(), np.full(x.size, y), z.ravel()], axis=1) for y in (20, 21)])
+    walk = gm.walk_leaves(6, seed=4321, clusters=6, steps=60)
+    walk = walk[walk[:, 1] >= 26]
+    sx, sz = np.meshgrid(np.arange(13, 19), np.arange(19, 25), indexing="ij")
+    slab = np.stack([sx.ravel(), np.full(sx.size, 50), sz.ravel()], axis=1)
+    return np.unique(np.concatenate([floor, walk, slab]).astype(np.int64), axis=0)
+
+
+def _block_leaves():
+    g = np.arange(5, 11)
+    return np.stack(np.meshgrid(g, g, g, indexing="ij"), axis=-1).reshape(-1, 3).astype(np.int64)
+
+
+def _from_leaves(depth, xyz, seed):
+    nrm = np.random.default_rng(seed).normal(size=(len(xyz), 3)).astype(np.float32)
+    return build_from_leaves(depth, xyz, nrm)
+
+
+def _ico2():
+    """The ico2 mesh of tests/voxelize_util.py as the CPU builds its pool: voxelize.voxelize, then the native
+    host builder -- byte-equal to native_builder.build_mesh_svo's pool by tests/test_gpu_voxelize.py."""
+    from raytracingtest_amd import native_builder as nb
+    from raytracingtest_amd import voxelize as vz
+    from tests import voxelize_util as vu
+    _, _, depth = vu.mesh("ico2")
+    codes, nrm, col, _, _ = vu.reference("ico2")
+    return nb.build_from_leaves(depth, vz.leaf_xyz(codes), nrm, col)
+
+
+POOL_NAMES = ("terrain", "walk7", "ico2", "block")
+
+
+@functools.lru_cache(maxsize=None)
+def pools():
+    """{name: (SVOData, leaves, cells, root)}: the scene's trees in upload order, `root` the descriptor offset
+    each is uploaded at (SetSVOBuffer(svo, root)); leaves and cells as geometry_model.model_of takes them.
+    20,127 leaves in all, 12,105 of them the mesh pool's: the cell cull keeps a family's float64 sets at a few
+    seconds, and they are computed once per case."""
+    trees = {"terrain": _from_leaves(6, _terrain_leaves(), 61), "walk7": gm.pool("walk7")[0], "ico2": _ico2(),
+             "block": _from_leaves(4, _block_leaves(), 41)}
+    out, root = {}, 0
+    for name in POOL_NAMES:
+        svo = trees[name]
+        leaves = svo.leaf_voxels()
+        leaves.setflags(write=False)
+        out[name] = (svo, leaves, gm.cells_of(leaves), root)
+        root += len(svo)
+    return out
+
+
+def n_nodes():
+    return sum(len(p[0]) for p in pools().values())
+
+
+# ---------------------------------------------------------------------------------- placements
+def _r32(R):
+    return np.asarray(R, np.float64).astype(np.float32)
+
+
+# (pool, scale_log2, position, rotation as float32): the committed sets
+SETS = {
+    # renders and shadows.  The 16-unit walk7 cube and the 8-unit sphere interpenetrate each other and the
+    # terrain's cube; the last object lies wholly outside the terrain's cube, over sky.
+    "scene": (
+        ("walk7", -1, (2.0, 2.5, 3.0), _r32(rot((1.0, 2.0, 0.5), 40.0))),
+        ("ico2", -2, (-3.0, -2.25, -1.0), _r32(rot((0.3, 1.0, 0.2), 65.0))),
+        ("block", -2, (-3.25, 4.5, -3.0), _r32(rot((0.2, 1.0, -0.1), 25.0))),      # over the sphere's other side
+        ("ico2", -3, (21.0, 1.0, 4.0), _r32(rot((1.0, 1.0, 0.3), 110.0))),
+    ),
+    # the query only: the limits of the table
+    "limits": (
+        ("walk7", -8, (1.5, 2.25, 3.0), _r32(rot((1.0, 2.0, 3.0), 37.0))),                 # a 1/8-unit cube
+        ("block", 8, (3000.0, 1000.0, -2000.0), _r32(rot((0.2, 1.0, 0.3), 50.0))),         # its cube holds the origins
+        ("block", 8, (2.0 ** 20 - 6000.0, 500.0, -800.0), _r32(rot((1.0, 0.5, -0.3), 20.0))),
+        ("block", 0, (40.0, 0.0, 0.0), _r32(axis_rotations()[7])),                         # an axis rotation
+        ("ico2", -1, (-20.0, 5.0, 10.0), _r32(rot((0.0, 1.0, 0.4), 75.0))),                # the same root twice
+        ("ico2", -3, (0.0, 10.0, -8.0), _r32(rot((1.0, 0.0, 1.0), 200.0))),
+        ("walk7", 2, (8.0, -4.0, 6.0), _r32(rot((0.5, 0.2, 1.0), 130.0))),                 # holds the origins too
+        ("walk7", -2, (-6.0, 3.0, 12.0), _r32(rot((1.0, 1.0, 1.0), 50.0))),
+    ),
+}
+
+
+def placements(set_name):
+    """The set as objects.make_objects takes it: [(root, scale_log2, position, rotation)]."""
+    return [(pools()[name][3], k, p, R) for name, k, p, R in SETS[set_name]]
+
+
+def candidates(set_name, terrain=True):
+    """[(pool name, k, p float64, R float64)] with the terrain (None when absent) as candidate 0."""
+    out = [("terrain", 0, np.zeros(3), np.eye(3)) if terrain else None]
+    for name, k, p, R in SETS[set_name]:
+        out.append((name, k, np.asarray(np.asarray(p, np.float32), np.float64), R.astype(np.float64)))
+    return out
+
+
+def to_world(cand, x_svo):
+    """Points of a candidate's SVO frame in the world, float64."""
+    _, k, p, R = cand
+    return p + 2.0 ** k * ((np.asarray(x_svo, np.float64) - 1.5) * 32.0) @ R.T
+
+
+def frame(cand, o, d, extra=None):
+    """(o', d', m, T) of world rays (o, d float64 [n, 3]) in a candidate's frame.  extra [n]: a world-space
+    (per-axis) uncertainty of the ray itself, added to the margin in the frame's units: a world vector e becomes
+    2^-k inv(R) e / 32, at most 2^-k max_j sum_i |inv(R)_ji| |e|_inf / 32 per axis."""
+    name, k, p, R = cand
+    if name == "terrain":
+        o2 = o / 32.0 + 1.5
+        m = K * ULP * np.maximum(1.0, np.abs(o2).max(axis=1))
+        return o2, d.copy(), m if extra is None else m + extra / 32.0, _cube_exit(o2, d)
+    Ri = np.linalg.inv(R)
+    s = 2.0 ** -k
+    q = o - p
+    o2 = (q @ Ri.T) * s / 32.0 + 1.5
+    d2 = (d @ Ri.T) * s
+    skew = R.T - Ri
+    e_o = (4.0 * U * s * (np.abs(q) @ np.abs(R)).max(axis=1) + s * np.abs(q @ skew.T).max(axis=1)) / 32.0
+    e_d = 3.0 * U * s * (np.abs(d) @ np.abs(R)).max(axis=1) + s * np.abs(d @ skew.T).max(axis=1)
+    T = _cube_exit(o2, d2)
+    m = K * ULP * np.maximum(1.0, np.abs(o2).max(axis=1)) + e_o + T * e_d
+    if extra is not None:
+        m = m + extra * s * np.abs(Ri).sum(axis=1).max() / 32.0
+    return o2, d2, m, T
+
+
+def cube_span(o, d):
+    """Float64 slab entry and exit of the cube [1, 2]^3 for rays of a frame (entry > exit: the ray misses it)."""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        a, b = (1.0 - o) / d, (2.0 - o) / d
+    return np.fmin(a, b).max(axis=1), np.fmax(a, b).min(axis=1)
+
+
+def _cube_exit(o, d):
+    tn, tf = cube_span(o, d)
+    return np.maximum(0.0, np.where(np.isfinite(tn), np.maximum(tn, tf), tf))
+
+
+def entered_face(cand, leaves_rows, o, d):
+    """The face through which the float64 ray (o, d of the candidate's frame) enters each leaf: the world-space
+    outward unit normal [n, 3] (the axis whose slab the ray enters last, rotated by R)."""
+    lo, hi, _ = gm.boxes(leaves_rows)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        tn = np.fmin((lo - o) / d, (hi - o) / d)
+    g = tn.argmax(axis=1)
+    r = np.arange(len(o))
+    N = np.zeros((len(o), 3))
+    N[r, g] = -np.sign(d[r, g])
+    Nw = N @ cand[3].T
+    return Nw / np.linalg.norm(Nw, axis=1, keepdims=True)
+
+
+# --------------------------------------------------------------------------------------- model
+def scene_model(set_name, traced, terrain=True, skip=None, extra=None):
+    """The scene sets of world rays as traced (sanitize_rays output), or of float64 rays (o, d, t_max) with a
+    world-space uncertainty `extra` [n] of their own (frame).  skip: (candidate [n], leaf row [n]), a
+    leaf per ray that is left out of its sets (the voxel a secondary ray starts on; candidate -1: none).
+    Returns {"frames": [(o', d', m, T) or None], "t_lim": [n],
+    "cand": [{mode: summary} or None], mode: the scene summary} -- n_may, n_must, first_cand / first (the
+    earliest may leaf), decided, must_entry / must_slack / must_cand (the earliest must leaf)."""
+    if isinstance(traced, tuple):
+        o, d, t_max = (np.asarray(a, np.float64) for a in traced)
+    else:
+        o, d, t_max = (traced[k].astype(np.float64) for k in ("origin", "dir", "t_max"))
+    t_lim = t_max / 32.0
+    n = len(o)
+    frames, cand = [], []
+    for c, cd in enumerate(candidates(set_name, terrain)):
+        if cd is None:
+            frames.append(None)
+            cand.append(None)
+            continue
+        _, leaves, cells, _ = pools()[cd[0]]
+        fr = frame(cd, o, d, extra)
+        sk = None if skip is None else np.where(skip[0] == c, skip[1], -1)
+        frames.append(fr)
+        cand.append(gm.model_of(leaves, cells, fr[0], fr[1], fr[2], t_lim=t_lim, skip=sk))
+    out = {"frames": frames, "t_lim": t_lim, "cand": cand}
+    live = [c for c, s in enumerate(cand) if s is not None]
+    r = np.arange(n)
+    for mode in (EXACT, HLSL):
+        def col(key, fill):
+            return np.stack([cand[c][mode][key] if cand[c] is not None else np.full(n, fill) for c in range(len(cand))])
+        fe, fs, oe = col("first_entry", np.inf), col("first_entry_s", np.inf), col("other_entry", np.inf)
+        is_must, first = col("first_is_must", False), col("first", -1)
+        me, ms = col("must_entry", np.inf), col("must_slack", 0.0)
+        n_may = sum(cand[c][mode]["n_may"] for c in live) if live else np.zeros(n, np.int64)
+        n_must = sum(cand[c][mode]["n_must"] for c in live) if live else np.zeros(n, np.int64)
+        cs = fe.argmin(axis=0)
+        rest = fe.copy()
+        rest[cs, r] = np.inf
+        decided = (n_may > 0) & is_must[cs, r] & (oe[cs, r] >= fs[cs, r]) & (rest.min(axis=0) >= fs[cs, r])
+        cm = me.argmin(axis=0)
+        out[mode] = {"n_may": n_may, "n_must": n_must, "first_cand": np.where(n_may > 0, cs, -1),
+                     "first": np.where(n_may > 0, first[cs, r], -1), "decided": decided,
+                     "must_entry": me[cm, r], "must_slack": np.where(n_must > 0, ms[cm, r], 0.0),
+                     "must_cand": np.where(n_must > 0, cm, -1),
+                     "cand_may": np.stack([cand[c][mode]["n_may"] if cand[c] is not None else np.zeros(n, np.int64)
+                                           for c in range(len(cand))]),
+                     "cand_must": np.stack([cand[c][mode]["n_must"] if cand[c] is not None else np.zeros(n, np.int64)
+                                            for c in range(len(cand))]),
+                     "cand_must_entry": me, "cand_first_entry": fe}
+    return out
+
+
+def min_dir(set_name, traced):
+    """The smallest |d'_k| over all candidates, per ray (float64)."""
+    o, d = (traced[0], traced[1]) if isinstance(traced, tuple) else (traced["origin"].astype(np.float64), traced["dir"].astype(np.float64))
+    return np.min([np.abs(frame(cd, o, d)[1]).min(axis=1) for cd in candidates(set_name)], axis=0)
+
+
+# ---------------------------------------------------------------------------------------- rays
+def _unit(rng, n):
+    v = rng.normal(size=(n, 3))
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def camera():
+    eye, target = np.array([-2.0, 7.0, -30.0]), np.array([7.0, -2.0, 0.0])
+    return Camera(position=tuple(eye), rotation=look_rotation(target - eye), fov=40.0)
+
+
+def _aimed(set_name, family, rng, count, aimed):
+    """count world rays of a family (float64 origins, directions, t_max), the candidates in turn."""
+    cands = candidates(set_name)
+    nc = len(cands)
+    o = np.zeros((count, 3))
+    d = np.zeros((count, 3))
+    t_max = np.full(count, np.inf)
+    which = np.arange(count) % nc
+    for c, cd in enumerate(cands):
+        at = np.flatnonzero(which == c)
+        leaves = pools()[cd[0]][1]
+        _, p, size = gm._targets(rng, leaves, len(at))
+        u = _unit(rng, len(at))
+        if family == "inside":                       # from inside the candidate's cube
+            src = rng.uniform(1.02, 1.98, (len(at), 3))
+        elif family == "between":                    # from half a voxel off a leaf face of another candidate
+            other = cands[(c + 1 + int(rng.integers(0, nc - 1))) % nc]
+            ol = pools()[other[0]][1]
+            lo, hi, sz = gm.boxes(ol)
+            k = rng.integers(0, len(ol), len(at))
+            q = lo[k] + rng.uniform(0.0, 1.0, (len(at), 3)) * sz[k, None]
+            axis, sign = rng.integers(0, 3, len(at)), rng.choice([-1.0, 1.0], len(at))
+            rr = np.arange(len(at))
+            q[rr, axis] = np.where(sign > 0, hi[k, axis], lo[k, axis]) + sign * 0.5 * sz[k]
+            src = None
+            ow = to_world(other, q)
+        else:                                        # far, tmax: 2 to 4 SVO units before the target
+            src = p - rng.uniform(2.0, 4.0, (len(at), 1)) * u
+        tw = to_world(cd, p)
+        if src is not None:
+            ow = to_world(cd, src)
+        dw = tw - ow
+        dist = np.linalg.norm(dw, axis=1)
+        o[at] = ow
+        d[at] = dw / dist[:, None] if aimed else _unit(rng, len(at))
+        if family == "tmax":                         # a first limit by the target; family_rays sets the aimed rays' own
+            t_max[at] = dist * np.array([0.5, 1.0, 1.5])[np.arange(len(at)) % 3]
+    return make_rays(o.astype(np.float32), d.astype(np.float32), t_max.astype(np.float32))
+
+
+def first_must_crossing(set_name, model, mode=EXACT):
+    """(grown entry, shrunk entry, shrunk exit) [n] of every ray's earliest must leaf over all candidates, in the
+    shared SVO parameter; nan where a ray has none."""
+    s = model[mode]
+    n = len(s["n_must"])
+    out = np.full((3, n), np.nan)
+    for c, cd in enumerate(candidates(set_name)):
+        k = np.flatnonzero(s["must_cand"] == c)
+        if len(k) and model["cand"][c] is not None:
+            o, d, m, _ = model["frames"][c]
+            p = gm.pairs_of(pools()[cd[0]][1], model["cand"][c][mode]["first_must"][k], o[k], d[k], m[k])
+            out[:, k] = p["entry_g"], p["entry_s"], p["exit_s"]
+    return out
+
+
+def _end_at_first_must(set_name, rays):
+    """The tmax family's limits, from the model alone: a third of the rays each ends before the grown entry of its
+    first must leaf (half way), in the middle of that leaf's shrunk crossing, and behind its shrunk exit (by half
+    its distance again) -- the first must leaf of the unlimited ray, which may be a nearer voxel than the one
+    aimed at.  Rays without a must leaf keep the limit they have."""
+    free = rays.copy()
+    free["t_max"] = np.inf
+    entry_g, entry_s, exit_s = first_must_crossing(set_name, scene_model(set_name, free))
+    kind = np.arange(len(rays)) % 3
+    t = np.where(kind == 0, 0.5 * entry_g, np.where(kind == 1, 0.5 * (entry_s + exit_s), 1.5 * exit_s)) * 32.0
+    out = rays.copy()
+    out["t_max"] = np.where(np.isnan(t), rays["t_max"], t.astype(np.float32))
+    return out
+
+
+def _usable(set_name, rays):
+    """Rays as traced whose direction the small-direction clamp leaves alone in every frame."""
+    traced, invalid = sanitize_rays(rays)
+    assert not invalid.any()
+    return traced[min_dir(set_name, traced) >= MIN_DIR]
+
+
+@functools.lru_cache(maxsize=None)
+def family_rays(set_name, family):
+    """The seeded batch of a family on a set, as traced, read-only: N_RAYS aimed rays plus up to N_RAYS / 4 strays
+    chosen by the model alone (125 model misses where the search finds them, and up to 125 others), as
+    geometry_model.family_rays does.  Rays with a component of some d' below 2^-22 are left out (by the model)."""
+    seed = 5000 + 100 * list(SETS).index(set_name) + FAMILIES.index(family)
+    if family in CAM_SIZES:
+        w, h = CAM_SIZES[family]
+        rays = _usable(set_name, camera_rays(*camera().uniforms(w, h), w, h))
+        assert len(rays) == w * h
+    else:
+        rng = np.random.default_rng(seed)
+        parts, misses, others = [_usable(set_name, _aimed(set_name, family, rng, N_RAYS + 50, True))[:N_RAYS]], 0, 0
+        assert len(parts[0]) == N_RAYS
+        if family == "tmax":
+            parts[0] = _end_at_first_must(set_name, parts[0])
+        for _ in range(8):
+            stray = _usable(set_name, _aimed(set_name, family, rng, 500, False))
+            empty = scene_model(set_name, stray)[EXACT]["n_may"] == 0
+            keep = np.zeros(len(stray), bool)
+            keep[np.flatnonzero(empty)[:N_RAYS // 8 - misses]] = True
+            keep[np.flatnonzero(~empty)[:N_RAYS // 8 - others]] = True
+            misses, others = misses + int((keep & empty).sum()), others + int((keep & ~empty).sum())
+            parts.append(stray[keep])
+            if misses >= N_RAYS // 8 and others >= N_RAYS // 8:
+                break
+        rays = np.concatenate(parts)
+    rays.setflags(write=False)
+    return rays
+
+
+@functools.lru_cache(maxsize=None)
+def case(set_name, family, terrain=True):
+    """(rays as traced, scene model) of a set and family, computed once."""
+    traced = family_rays(set_name, family)
+    return traced, scene_model(set_name, traced, terrain)
+
+
+def order_classes(set_name, model, mode):
+    """Masks of the rays on which the table order and the entry skip of the rule matter, from the model alone.
+    skip: the earliest must leaf lies in candidate c, and a later object's cube, which the ray crosses, begins
+    behind that leaf (its entry skip must drop the object, and drops nothing nearer).  replace: the earliest
+    must leaf lies in an object and an earlier table entry has a must leaf too, behind it (the later entry
+    must replace the best).  keep: a later object has a must leaf behind the earliest one's and its cube begins
+    before it (it is walked, hits, and must not be taken)."""
+    s = model[mode]
+    n = len(s["n_may"])
+    mc, me = s["must_cand"], s["must_entry"]
+    skip, replace, keep = np.zeros(n, bool), np.zeros(n, bool), np.zeros(n, bool)
+    for c in range(1, len(model["frames"])):
+        o, d, _, _ = model["frames"][c]
+        tn, tf = cube_span(o, d)
+        crossed = (tn <= tf) & (tf >= 0.0)
+        entry = np.maximum(tn, 0.0)
+        later = (mc >= 0) & (mc < c)
+        skip |= later & crossed & (entry > me) & (entry <= model["t_lim"])
+        keep |= later & crossed & (entry < me) & (s["cand_must"][c] > 0)
+        replace |= (mc == c) & (s["cand_must"][:c] > 0).any(axis=0)
+    return {"skip": skip, "replace": replace, "keep": keep}
+
+
+def ids_of_records(set_name, traced, hits, model):
+    """Object ids for the records of a render, which writes none: a hit's parent names its pool, and where a pool
+    is placed more than once, the placement in whose frame the record's t lies nearest its voxel's float64 entry
+    (-1 on misses; an AssertionError if a parent lies in no pool)."""
+    ids = np.full(len(hits), -1, np.int64)
+    hit = np.flatnonzero((hits["flags"] & gm.FLAG_HIT) != 0)
+    parent = hits["parent"][hit].astype(np.int64)
+    best = np.full(len(hit), np.inf)
+    got = np.full(len(hit), -1, np.int64)
+    for c, cd in enumerate(candidates(set_name)):
+        svo, leaves, _, root = pools()[cd[0]]
+        k = np.flatnonzero((parent >= root) & (parent < root + len(svo)))
+        if not len(k):
+            continue
+        at = hit[k]
+        o, d, m, _ = model["frames"][c]
+        p = gm.pairs_of(leaves, gm.leaf_rows_of(leaves, hits[at], root), o[at], d[at], m[at])
+        dev = np.where(p["may"], np.abs(hits["t"][at].astype(np.float64) / 2048.0 - p["entry_true"]), 1e300)
+        better = dev < best[k]
+        best[k] = np.where(better, dev, best[k])
+        got[k] = np.where(better, c, got[k])
+    assert (got >= 0).all(), f"{(got < 0).sum()} records whose parent lies in no pool"
+    ids[hit] = got
+    return ids
+
+
+def decided_share(models, mode):
+    some = np.concatenate([m[mode]["n_may"] > 0 for m in models])
+    return float(np.concatenate([m[mode]["decided"] for m in models])[some].mean())
+
+
+# ---------------------------------------------------------------------------------- assertions
+def scene_check(set_name, traced, mode, model, hits, ids, voxel, position, normals, terrain=True, skip=None,
+                extra_flags=0, what="", masks=None):
+    """Section-3 assertions on any tracer's scene records: hits (HIT_DTYPE), ids (int32), voxel keys, positions
+    ([n, 4] f32, None: not checked) of world rays `traced`; model: scene_model's result for them; normals:
+    {pool name: [leaves, 3] f32} the record normal of every leaf from a stand-alone trace of the pool.
+    skip: scene_model's; a record that reports the skipped leaf itself is counted (self_hits) and otherwise
+    left alone.  extra_flags: flag bits a render may add.  masks: a dict that receives self_hit [n] and rows
+    [n] (the reported leaf rows, -1 on misses).  Returns the figures for the record."""
+    s = model[mode]
+    n = len(traced)
+    cands = candidates(set_name, terrain)
+    flags = hits["flags"]
+    voxel = np.asarray(voxel, np.uint64)
+    ids = np.asarray(ids, np.int64)
+    assert not np.any(flags & (gm.FLAG_CAP | gm.FLAG_OVERFLOW)), f"{what}: iteration-cap or overflow flag"
+    assert not np.any(flags & ~np.uint16(gm.FLAG_HIT | extra_flags)), f"{what}: unexpected flag bits {np.unique(flags)}"
+    hit = (flags & gm.FLAG_HIT) != 0
+    assert np.array_equal(hit, hits["parent"] != 0xFFFFFFFF), f"{what}: hit bit and parent disagree"
+    assert np.array_equal(ids == -1, ~hit), f"{what}: id -1 and the misses disagree"
+    assert np.all((ids[hit] >= (0 if terrain else 1)) & (ids[hit] < len(cands))), f"{what}: an id outside the table"
+    assert np.all(voxel[~hit] == ~np.uint64(0)) and np.all(np.isinf(hits["t"][~hit])), f"{what}: a miss carries a key or a t"
+    rows = np.full(n, -1, np.int64)
+    self_hit = np.zeros(n, bool)
+    gap_units, dev_units = 0.0, 0.0
+    per_cand = []
+    for c, cd in enumerate(cands):
+        at = np.flatnonzero(ids == c)
+        per_cand.append(int(len(at)))
+        if cd is None or not len(at):
+            continue
+        _, leaves, _, root = pools()[cd[0]]
+        o, d, m, _ = model["frames"][c]
+        try:
+            rows[at] = gm.leaf_rows_of(leaves, hits[at], root)
+        except AssertionError as e:
+            raise AssertionError(f"{what}: candidate {c}: {e}") from None
+        rw = rows[at]
+        assert np.array_equal(hits["hit_scale"][at], 23 - leaves[rw, 2]), f"{what}: candidate {c}: hit_scale != 23 - L"
+        assert np.array_equal(voxel[at], gm.voxel_keys(leaves[rw])), f"{what}: candidate {c}: voxel key"
+        if skip is not None:
+            self_hit[at] = (skip[0][at] == c) & (skip[1][at] == rw)
+        ok = ~self_hit[at]
+        p = gm.pairs_of(leaves, rw, o[at], d[at], m[at], t_lim=model["t_lim"][at])
+        off = ok & ~p["may"]
+        assert not off.any(), f"{what}: candidate {c}: {off.sum()} reported voxels off the ray, first rays {at[off][:5]}"
+        t = hits["t"][at].astype(np.float64) / 2048.0
+        tol = m[at] / np.abs(d[at]).min(axis=1)
+        dev = np.abs(t - p["entry_true"])
+        bad = ok & (dev > tol)
+        assert not bad.any(), f"{what}: candidate {c}: {bad.sum()} entry distances off, worst {np.max(dev / tol):.2f} " \
+                              f"tolerances (ray {at[np.argmax(dev / tol)]})"
+        late = ok & (p["entry_g"] > s["must_entry"][at] + s["must_slack"][at])
+        assert not late.any(), f"{what}: candidate {c}: {late.sum()} rays report a voxel behind a must leaf, first {at[late][:5]}"
+        if ok.any():
+            gap_units = max(gap_units, float(np.max((p["gap"] / m[at])[ok])))
+            dev_units = max(dev_units, float(np.max((dev / tol)[ok])))
+        # the world normal: the pool's own record normal of that leaf, rotated
+        got = np.stack([hits["nx"][at], hits["ny"][at], hits["nz"][at]], axis=1)
+        mn = normals[cd[0]][rw]
+        if c == 0:
+            assert got.tobytes() == mn.tobytes(), f"{what}: a terrain normal is not the record's"
+        else:
+            R = cd[3]
+            want = mn.astype(np.float64) @ R.T
+            bound = 4.0 * U * (np.abs(mn.astype(np.float64)) @ np.abs(R).T)
+            wrong = np.abs(got.astype(np.float64) - want) > bound
+            assert not wrong.any(), f"{what}: candidate {c}: {wrong.any(axis=1).sum()} world normals off R m, first {at[wrong.any(axis=1)][:5]}"
+        if position is not None:
+            x = np.asarray(position, np.float32)[at, :3].astype(np.float64) / 2.0       # the frame's [-16, 16]^3
+            xw = cd[2] + 2.0 ** cd[1] * x @ cd[3].T
+            back = ((xw - cd[2]) @ np.linalg.inv(cd[3]).T) * 2.0 ** -cd[1] / 32.0 + 1.5
+            lo, hi, _ = gm.boxes(leaves[rw])
+            outside = np.maximum(lo - back, back - hi).max(axis=1) > m[at]
+            assert not outside.any(), f"{what}: candidate {c}: {outside.sum()} positions outside their voxel"
+    live = ~self_hit
+    lost = live & (s["n_must"] > 0) & ~hit
+    assert not lost.any(), f"{what}: {lost.sum()} rays with a must leaf came back as misses, first {np.flatnonzero(lost)[:5]}"
+    ghost = live & (s["n_may"] == 0) & (hit | ((flags & ~np.uint16(extra_flags)) != 0))
+    assert not ghost.any(), f"{what}: {ghost.sum()} rays with an empty may set are no plain miss, first {np.flatnonzero(ghost)[:5]}"
+    wrong = live & s["decided"] & ((ids != s["first_cand"]) | (rows != s["first"]))
+    assert not wrong.any(), f"{what}: {wrong.sum()} decided rays report another candidate or leaf, first {np.flatnonzero(wrong)[:5]}"
+    if masks is not None:
+        masks.update(self_hit=self_hit, rows=rows)
+    return {"rays": int(n), "hits": int(hit.sum()), "hits_per_candidate": per_cand, "must": int((s["n_must"] > 0).sum()),
+            "model_misses": int((s["n_may"] == 0).sum()), "decided_share": round(decided_share([model], mode), 4),
+            "max_gap_margins": round(gap_units, 4), "max_entry_dev_margins": round(dev_units, 4),
+            "self_hits": int(self_hit.sum())}
+
+
+# ------------------------------------------------------------------------------------- shadows
+SHADOW_CLASSES = ("terrain_by_terrain_alone", "terrain_by_object_alone", "object_by_terrain_alone",
+                  "object_by_another_object_alone", "object_by_itself_alone", "terrain_lit", "object_lit")
+
+
+def shadow_model(set_name, rays, hits, ids, light):
+    """The float64 sets of every hit pixel's shadow ray (geometry_model.shadow_rays on the finished record, its
+    start leaf stays in the sets) and the class of every hit pixel: (pixel indices, scene model, {mode:
+    {class: mask over those pixels}})."""
+    px = np.flatnonzero((hits["flags"] & gm.FLAG_HIT) != 0)
+    sr = gm.shadow_rays(rays[px], hits[px], light)
+    traced, invalid = sanitize_rays(sr, raw=True)
+    assert not invalid.any()
+    model = scene_model(set_name, traced)
+    own = np.asarray(ids, np.int64)[px]
+    r = np.arange(len(px))
+    classes = {}
+    for mode in (EXACT, HLSL):
+        may, must = model[mode]["cand_may"] > 0, model[mode]["cand_must"] > 0
+        obj_may, obj_must = may[1:], must[1:]
+        own_must = must[own, r] & (own > 0)
+        own_may = may[own, r] & (own > 0)
+        other_must = (obj_must.sum(axis=0) - own_must) > 0
+        other_may = (obj_may.sum(axis=0) - own_may) > 0
+        on_t, on_o = own == 0, own > 0
+        classes[mode] = {
+            "terrain_by_terrain_alone": on_t & must[0] & ~obj_may.any(axis=0),
+            "terrain_by_object_alone": on_t & obj_must.any(axis=0) & ~may[0],
+            "object_by_terrain_alone": on_o & must[0] & ~obj_may.any(axis=0),
+            "object_by_another_object_alone": on_o & other_must & ~may[0] & ~own_may,
+            "object_by_itself_alone": on_o & own_must & ~may[0] & ~other_may,
+            "terrain_lit": on_t & (model[mode]["n_may"] == 0), "object_lit": on_o & (model[mode]["n_may"] == 0)}
+    return px, model, classes
+
+
+def shadow_check(set_name, rays, hits, ids, light, mode, what=""):
+    """A pixel's shadow bit (flag bit 3) must be set when some candidate has a must leaf on its float64 shadow
+    ray and clear when the scene may set is empty; a miss never carries it.  Returns the counts."""
+    flags = hits["flags"]
+    hit = (flags & gm.FLAG_HIT) != 0
+    assert not np.any(flags[~hit] & 8), f"{what}: a miss pixel carries the shadow bit"
+    px, model, classes = shadow_model(set_name, rays, hits, ids, light)
+    s = model[mode]
+    bit = (flags[px] & 8) != 0
+    must, empty = s["n_must"] > 0, s["n_may"] == 0
+    assert bit[must].all(), f"{what}: {np.count_nonzero(~bit[must])} pixels whose shadow ray must hit are lit, first {px[must & ~bit][:5]}"
+    assert not bit[empty].any(), f"{what}: {np.count_nonzero(bit[empty])} pixels whose shadow ray meets nothing are " \
+                                 f"shadowed, first {px[empty & bit][:5]}"
+    out = {k: int(v.sum()) for k, v in classes[mode].items()}
+    out.update(hit_pixels=int(len(px)), must_shadowed=int(must.sum()), must_lit=int(empty.sum()),
+               undecided=int((~must & ~empty).sum()), undecided_shadowed=int(bit[~must & ~empty].sum()))
+    return out
+
+
+# -------------------------------------------------------------------------------- point lights
+# (position, range, colour): one light inside the scene, one out of range for most hits, one far away
+LIGHTS = (((1.0, 4.0, -7.0), 40.0, (3.0, 2.5, 2.0)),
+          ((-5.5, 2.5, -4.5), 11.0, (0.5, 2.0, 4.0)),
+          ((300.0, 420.0, -260.0), 2.0 ** 12, (8.0, 12.0, 16.0)))
+STEEP = 0.1
+
+
+def record_rows(set_name, hits, ids):
+    """The leaf row of every record in its candidate's pool (-1 on misses)."""
+    rows = np.full(len(hits), -1, np.int64)
+    for c, cd in enumerate(candidates(set_name)):
+        at = np.flatnonzero(np.asarray(ids) == c)
+        if len(at):
+            _, leaves, _, root = pools()[cd[0]]
+            rows[at] = gm.leaf_rows_of(leaves, hits[at], root)
+    return rows
+
+
+def float64_origins(set_name, rays, hits, ids):
+    """Where the light rule's origin Q of every record belongs, from float64 geometry alone: the entry point of
+    the float64 frame ray into the reported leaf, its coordinate on the entered axis set to the face plus 2^-6 of
+    the voxel's side outward (svo_scene_light.h (a): reflection.entry_face's step 3), taken to the world by
+    p + 2^k R.  Returns {"Q" [n, 3], "bound" [n], "ambiguous" [n], "normal" [n, 3] the face's world-space outward
+    unit normal, "rows"}; rows of misses hold zeros.
+
+    bound: how far (per axis, world units) the f32 rule's Q may lie from that point.  In the frame, SVO units,
+    with m the candidate's margin (it holds e_o and T e_d): the rule's lateral coordinates are
+    fl(o'_j + fl(tw d'_j)) with tw the RECORD's t / 64 -- o'_j is off by at most e_o, d'_j by e_d (tw e_d <= T e_d),
+    and the record's t is off the float64 entry by at most m / min_k |d'_k| (scene_check asserts that), which
+    moves the point by |d'_j| m / min_k |d'_k|; the product and the sum round once each, at most
+    2u (|o'_j - 1.5| + 2 t |d'_j|).  The entered coordinate is dyadic and exact.  So
+        b = m (1 + |d'|_inf / min_k |d'_k|) + 4u (|o' - 1.5|_inf + t |d'|_inf)
+    and in the world  bound = 32 * 2^k max_i sum_j |R_ij| b + 4 ulp_f32(M),  M = 2^k sum_j |Q'_j| + |p|_inf, the
+    last term the bound of test_world_origin_within_four_ulp_of_float64 on the step Q' -> Q.
+    ambiguous: the two latest slab entries lie closer than their own uncertainty m / |d'_g| + m / |d'_h|, so f32
+    may enter through the other face; such records have no single float64 origin and are counted, not checked."""
+    ids = np.asarray(ids, np.int64)
+    n = len(ids)
+    rows = record_rows(set_name, hits, ids)
+    o = rays["origin"].astype(np.float64)
+    d = rays["dir"].astype(np.float64)
+    Q, N = np.zeros((n, 3)), np.zeros((n, 3))
+    bound, amb = np.zeros(n), np.zeros(n, bool)
+    for c, cd in enumerate(candidates(set_name)):
+        at = np.flatnonzero(ids == c)
+        if not len(at):
+            continue
+        _, k, p, R = cd
+        leaves = pools()[cd[0]][1][rows[at]]
+        o2, d2, m, _ = frame(cd, o[at], d[at])
+        lo, hi, side = gm.boxes(leaves)
+        tn = np.fmin((lo - o2) / d2, (hi - o2) / d2)
+        order = np.argsort(tn, axis=1)
+        r = np.arange(len(at))
+        g, h2 = order[:, 2], order[:, 1]
+        ad = np.abs(d2)
+        amb[at] = tn[r, g] - tn[r, h2] <= m / ad[r, g] + m / ad[r, h2]
+        te = np.maximum(tn[r, g], 0.0)
+        q = o2 + te[:, None] * d2
+        out = -np.sign(d2[r, g])
+        q[r, g] = np.where(d2[r, g] > 0, lo[r, g], hi[r, g]) + out * side * 2.0 ** -6
+        Q[at] = to_world(cd, q)
+        nf = np.zeros((len(at), 3))
+        nf[r, g] = out
+        nw = nf @ R.T
+        N[at] = nw / np.linalg.norm(nw, axis=1, keepdims=True)
+        b = m * (1.0 + ad.max(axis=1) / ad.min(axis=1)) + 4.0 * U * (np.abs(o2 - 1.5).max(axis=1) + te * ad.max(axis=1))
+        M = 2.0 ** k * np.abs((q - 1.5) * 32.0).sum(axis=1) + np.abs(p).max()
+        bound[at] = 32.0 * 2.0 ** k * np.abs(R).sum(axis=1).max() * b + 4.0 * np.spacing(M.astype(np.float32)).astype(np.float64)
+    return {"Q": Q, "bound": bound, "ambiguous": amb, "normal": N, "rows": rows}
+
+
+def segment_case(set_name, rays, hits, ids, segments, lights):
+    """The light segments {Q, t_max 1, L} that svo_scene_light_rays (or its numpy statement) wrote for world rays
+    `rays` (as traced) and their records, segments [n * n_lights], held to float64: every live segment of a
+    record whose entered face is not ambiguous must start within float64_origins' bound of the float64 origin
+    and point from there to the light (within bound + 2u |L|_inf: L = fl(p_l - Q)).  Then the float64 sets of the
+    segments as traced, the record's own leaf left out.  Returns a dict: `at` the indices of the checked segments
+    (live, no component of any d' below 2^-22), `traced`, `skip`, `model`, `steep` (the segment leaves the float64
+    entered face with N.L / |L| >= 0.1), `unchecked`, `ambiguous` (live segments whose origin was not checked)
+    and `max_origin_dev` (the largest distance from the float64 origin in bounds)."""
+    ids = np.asarray(ids, np.int64)
+    n_lights = len(lights)
+    f = float64_origins(set_name, rays, hits, ids)
+    live = np.flatnonzero(segments["t_max"] == np.float32(1.0))
+    src = live // n_lights
+    pl = np.array([np.asarray(l[0], np.float32) for l in lights], np.float64)[live % n_lights]
+    dev = np.abs(segments["origin"][live].astype(np.float64) - f["Q"][src]).max(axis=1)
+    sure = ~f["ambiguous"][src]
+    far = sure & (dev > f["bound"][src])
+    assert not far.any(), f"{far.sum()} segment origins off the float64 entry point, worst {np.max((dev / f['bound'][src])[sure]):.2f} " \
+                          f"bounds (segment {live[far][0]})"
+    want = pl - f["Q"][src]
+    ddev = np.abs(segments["dir"][live].astype(np.float64) - want).max(axis=1)
+    off = sure & (ddev > f["bound"][src] + 2.0 * U * np.abs(want).max(axis=1))
+    assert not off.any(), f"{off.sum()} segment directions do not point from the float64 origin to the light"
+    traced, invalid = sanitize_rays(segments[live])
+    assert not invalid.any()
+    ok = min_dir(set_name, traced) >= MIN_DIR
+    at, traced, src = live[ok], traced[ok], src[ok]
+    skip = (ids[src], f["rows"][src])
+    L = traced["dir"].astype(np.float64)
+    cos = (f["normal"][src] * L).sum(axis=1) / np.linalg.norm(L, axis=1)
+    return {"at": at, "traced": traced, "skip": skip, "model": scene_model(set_name, traced, skip=skip),
+            "steep": cos >= STEEP, "unchecked": int((~ok).sum()), "ambiguous": int((~sure).sum()),
+            "max_origin_dev": round(float(np.max((dev / f["bound"][live // n_lights])[sure])), 4) if sure.any() else 0.0}
+
+
+def float64_segments(set_name, rays, hits, ids, light):
+    """The float64 segment of every record toward one light, for the render route: from float64_origins' Q to
+    the light's position, t_max 1, its sets with the record's own leaf left out and the margin grown by what the
+    f32 segment may differ by, bound + 2u |L|_inf (a point Q + t L, t in [0, 1], moves by at most that).
+    Returns (model, usable [n]: a hit whose entered face is not ambiguous and whose segment has no d' component
+    below 2^-22, on_object [n])."""
+    ids = np.asarray(ids, np.int64)
+    f = float64_origins(set_name, rays, hits, ids)
+    pl = np.asarray(np.asarray(light[0], np.float32), np.float64)
+    L = pl - f["Q"]
+    rays64 = (f["Q"], L, np.ones(len(ids)))
+    extra = f["bound"] + 2.0 * U * np.abs(L).max(axis=1)
+    usable = (ids >= 0) & ~f["ambiguous"] & (min_dir(set_name, rays64) >= MIN_DIR)
+    model = scene_model(set_name, rays64, skip=(ids, f["rows"]), extra=extra)
+    return model, usable, ids > 0

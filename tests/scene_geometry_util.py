@@ -1,0 +1,174 @@
+"""Shared helpers of the float64 scene tests (tests/test_scene_geometry_model.py, tests/test_gpu_scene_geometry.py):
+the oracle-side scene (object_util.scene_expected over scene_geometry_model's pools), the record normal of every
+leaf, the two point-light checks, which take any tracer's outputs, and the record file."""
+import functools
+import json
+import os
+
+import numpy as np
+
+from raytracingtest_amd.query import make_rays
+from tests import geometry_model as gm
+from tests import object_util as ou
+from tests import scene_geometry_model as sg
+from tests.conftest import ROOT
+from tests.geometry_model import EXACT, HLSL
+from tests.query_util import oracle_svo, oracle_trace
+
+RECORD = os.path.join(ROOT, "profiles", "scene_geometry_truth.json")
+MODE_NAME = {EXACT: "exact", HLSL: "hlsl"}
+QUERY_FAMILIES = {"scene": ("far", "inside", "between", "tmax", "camera", "camera_small"), "limits": ("far", "inside", "between", "tmax")}
+QUERY_CASES = [(s, f, t) for s in QUERY_FAMILIES for f in QUERY_FAMILIES[s] for t in (True, False)
+               if t or f not in sg.CAM_SIZES]          # a render always has its terrain
+CLASS_FLOOR = 20
+SEGMENT_FAMILY = "camera_small"      # the records whose light segments the query route checks (about 3,000 segments)
+
+
+class OracleScene:
+    """scene_geometry_model's pools as object_util.scene_expected takes a scene."""
+
+    def __init__(self):
+        self.terrain = sg.pools()["terrain"][0]
+        self.by_root = {p[3]: p[0] for p in sg.pools().values()}
+
+    def tree_of_root(self, root):
+        return self.by_root[root]
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_scene():
+    return OracleScene()
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_normals():
+    """{pool: [leaves, 3] f32}: every leaf's record normal, from the oracle tracing the pool stand-alone with a
+    ray that starts at the leaf's centre (the walk ends in the voxel that holds the origin)."""
+    from oracle import oracle
+    oracle.lib()
+    out = {}
+    for name, (svo, leaves, _, _) in sg.pools().items():
+        lo, hi, _ = gm.boxes(leaves)
+        rays = make_rays(((0.5 * (lo + hi) - 1.5) * 32.0).astype(np.float32), np.tile(np.float32([0.3, 0.5, 0.8]), (len(leaves), 1)))
+        hits, _, _ = oracle_trace(oracle, oracle_svo(oracle, svo), rays, EXACT)
+        assert np.array_equal(gm.leaf_rows_of(leaves, hits), np.arange(len(leaves)))
+        out[name] = np.stack([hits["nx"], hits["ny"], hits["nz"]], axis=1)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_query(set_name, family, mode, terrain=True, raw=False):
+    from oracle import oracle
+    oracle.lib()
+    traced, _ = sg.case(set_name, family, terrain)
+    return ou.scene_expected(oracle, oracle_scene(), traced, sg.placements(set_name), mode, raw=raw, terrain=terrain)
+
+
+def check_shadow_classes(fig, what):
+    for k in sg.SHADOW_CLASSES:
+        assert fig[k] >= CLASS_FLOOR, f"{what}: {fig[k]} pixels of class {k}"
+
+
+# -------------------------------------------------------------------------------- point lights
+def light_segments_check(rays, hits, ids, segments, trace, mode, what):
+    """The query route of the point lights: `segments` = the scene-light rays of a scene query's records (rays,
+    hits, ids) toward sg.LIGHTS; trace(segments) -> (hits, ids, voxel, position) is the occlusion query.
+    segment_case holds every segment's origin and direction to the float64 entry point; the checked segments then
+    go through scene_check under t_lim = 1 with the record's own leaf left out; segments reported as occluded by
+    their own start leaf are counted, and among the steep ones there must be none."""
+    k = len(sg.LIGHTS)
+    case = sg.segment_case("scene", rays, hits, ids, segments, sg.LIGHTS)
+    at = case["at"]
+    src_ids = np.asarray(ids)[at // k]
+    for light in range(k):                       # every light has segments from the terrain and from objects
+        assert ((at % k == light) & (src_ids == 0)).sum() >= CLASS_FLOOR and ((at % k == light) & (src_ids > 0)).sum() >= CLASS_FLOOR
+    h2, i2, v2, p2 = trace(case["traced"])
+    masks = {}
+    fig = sg.scene_check("scene", case["traced"], mode, case["model"], h2, i2, v2, p2, oracle_normals(), skip=case["skip"],
+                         what=what, masks=masks)
+    s = case["model"][mode]
+    on_o = case["skip"][0] > 0
+    fig.update(segments=int(len(at)), unchecked=case["unchecked"], ambiguous_face=case["ambiguous"],
+               max_origin_dev_bounds=case["max_origin_dev"], steep=int(case["steep"].sum()),
+               self_hits_steep=int((masks["self_hit"] & case["steep"]).sum()),
+               must_occluded_terrain=int(((s["n_must"] > 0) & ~on_o).sum()), must_occluded_object=int(((s["n_must"] > 0) & on_o).sum()),
+               clear_terrain=int(((s["n_may"] == 0) & ~on_o).sum()), clear_object=int(((s["n_may"] == 0) & on_o).sum()))
+    for key in ("must_occluded_terrain", "must_occluded_object", "clear_terrain", "clear_object"):
+        assert fig[key] >= CLASS_FLOOR, f"{what}: {key} {fig[key]}"
+    assert fig["self_hits_steep"] == 0, f"{what}: {fig['self_hits_steep']} steep segments are occluded by the voxel they start on"
+    return fig
+
+
+def light_render_case(rays, hits, ids, light, mode, contributes):
+    """The render route of one point light, for the records of a render with objects (rays: its camera rays;
+    contributes [n] bool: the pixels the light changes when it casts no shadow).  The reference is float64 alone:
+    scene_geometry_model.float64_segments -- from the float64 entry point of the camera ray into the reported
+    leaf, pushed 2^-6 of the voxel's side out of the entered face as svo_scene_light.h states, to the light -- with
+    the derived distance of the rule's f32 origin from that point added to the margin.  (The issue's bound for that
+    distance, test_world_origin_within_four_ulp_of_float64's, covers only the step Q' -> Q; float64_origins
+    derives the rest.)  Returns (pixel indices, must-occluded mask, clear mask, on-object mask) over the
+    contributing pixels that are checked, and the counts per class, each at least CLASS_FLOOR."""
+    px = np.flatnonzero(np.asarray(ids) >= 0)
+    model, usable, on_object = sg.float64_segments("scene", rays[px], hits[px], np.asarray(ids)[px], light)
+    keep = usable & contributes[px]
+    s = model[mode]
+    must, clear, on_o = (s["n_must"] > 0)[keep], (s["n_may"] == 0)[keep], on_object[keep]
+    fig = {"contributing": int(contributes.sum()), "checked": int(keep.sum()), "occluded_terrain": int((must & ~on_o).sum()),
+           "occluded_object": int((must & on_o).sum()), "clear_terrain": int((clear & ~on_o).sum()),
+           "clear_object": int((clear & on_o).sum())}
+    for key in ("occluded_terrain", "occluded_object", "clear_terrain", "clear_object"):
+        assert fig[key] >= CLASS_FLOOR, f"{key}: {fig[key]} pixels"
+    return px[keep], must, clear, on_o, fig
+
+
+# ------------------------------------------------------------------------------------ the record
+def compact(d):
+    """Figures with one entry where both stack modes gave the same: {"exact": x, "hlsl": x} -> {"exact=hlsl": x}."""
+    if isinstance(d, list):
+        return " ".join(str(v) for v in d)
+    if not isinstance(d, dict):
+        return d
+    d = {k: compact(v) for k, v in d.items()}
+    if set(d) == {"exact", "hlsl"} and d["exact"] == d["hlsl"]:
+        return {"exact=hlsl": d["exact"]}
+    return d
+
+
+def differing(mine, theirs, path=""):
+    """(what of `mine` differs from `theirs`, the paths of the entries that are equal and left out)."""
+    if isinstance(mine, dict) and isinstance(theirs, dict):
+        out, same = {}, []
+        for k, v in mine.items():
+            if k in theirs and v == theirs[k]:
+                same.append(f"{path}{k}")
+            elif k in theirs:
+                sub, s2 = differing(v, theirs[k], f"{path}{k}/")
+                out[k] = sub
+                same += s2
+            else:
+                out[k] = v
+        return out, same
+    return mine, []
+
+
+def update_record(key, value, path=RECORD):
+    """Merge one producer's figures into the file, as tests/test_geometry_model.update_record does: the oracle's run
+    (tests/test_scene_geometry_model.py) rewrites the file and keeps the GPU's entry, the GPU's run
+    (tests/test_gpu_scene_geometry.py) adds its own.  The GPU's entry holds only what differs from the oracle's
+    figures of the same name, and lists the names that are equal under `identical_to_oracle`."""
+    rec = json.load(open(path)) if os.path.exists(path) else {}
+    value = compact(value)
+    if key == "oracle":
+        gpu = {n: p.get("gpu") for n, p in rec.get("sets", {}).items()}
+        rec = value
+        for n, g in gpu.items():
+            if g is not None and n in rec["sets"]:
+                rec["sets"][n]["gpu"] = g
+    else:
+        for n, g in value.items():
+            entry = rec.setdefault("sets", {}).setdefault(n, {})
+            diff, same = differing(g, entry.get("oracle", {}))
+            entry[key] = dict(diff, identical_to_oracle=same)
+    with open(path, "w") as fh:
+        json.dump(rec, fh, indent=1, sort_keys=True)
+        fh.write("\n")
