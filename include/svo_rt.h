@@ -928,6 +928,97 @@ int svo_scene_light_rays_host(svo_ctx *ctx, const svo_ray *rays, size_t n, uint3
                               const uint64_t *voxel, const int32_t *object, const svo_object *objects, int n_objects,
                               const svo_light *lights, int n_lights, svo_ray *rays_out);
 
+/* Volume queries: which voxels does a world-space volume touch?  Collision broad-phase, spawn placement,
+ * trigger volumes, editor selection.  The reference has no volume query of any kind (a documented addition).
+ * A batch of caller-supplied shapes, each an axis-aligned box or a sphere; per shape the number of leaf
+ * voxels it touches, the first K of them as contact records, and one bit of a hit mask.  The query reads the
+ * node pool only: it leaves every piece of render state alone (dispatch orders, tile costs, beam starts,
+ * view-change detection, kernel-timing records, the progressive frame), like svo_trace_rays.
+ *
+ * The overlap rule (csrc/svo_overlap.h; Python: overlap.py; INTEGRATION.md "Volume queries").  Exact: voxel
+ * boxes are dyadic numbers, the box test is compares only and the sphere test is monotone under rounding, so
+ * the result equals a brute force over all leaves under the same test -- no margins.
+ *  - Shape (svo_shape, 32 bytes, 16-byte aligned like svo_ray).  SVO_SHAPE_BOX: the closed box [p, q].
+ *    SVO_SHAPE_SPHERE: centre p, radius q[0]; q[1], q[2] and reserved are 0.  INVALID: a non-finite number
+ *    among p and q, p_k > q_k in a box, a negative radius, an unknown kind.  An invalid shape is not walked:
+ *    count 0, visits 0, flags 0x10 (SVO_HIT_INVALID_RAY's value), no contacts, mask bit 0.
+ *  - Frame: the tree's own world convention, the cube [-16, 16]^3.  The root descriptor is level 0; a child at
+ *    level L with integer coordinates i has side = 2^(5 - L), lo_k = i_k side - 16, hi_k = lo_k + side, all
+ *    exact in f32.  Slot c of a descriptor is the child at offset (c & 1, c >> 1 & 1, c >> 2 & 1); its valid
+ *    bit is valid8 >> c & 1 and its descriptor first + popcount(nonleaf8 & ((1 << c) - 1)).
+ *  - Touch.  Box: lo_k <= q_k and hi_k >= p_k for every k (closed intervals, exact compares).  Sphere:
+ *    e_k = max(max(lo_k - p_k, p_k - hi_k), 0), d2 = (e0 e0 + e1 e1) + e2 e2, each operation one IEEE f32
+ *    rounding, no fma; touch iff d2 <= r r (ordered).
+ *  - Walk: depth-first from `root`, slots 0 .. 7 ascending.  `visits` counts descriptor fetches; an index at
+ *    or past the uploaded nodes reads the zero descriptor.  A fetch that would make visits exceed max_visits
+ *    sets flag bit 1 (budget) and ends the walk: count and contacts are those found so far.  For each valid
+ *    child that touches: if its non-leaf bit is clear, or its level equals coarse_level (when non-zero), it
+ *    is a result voxel: count += 1, stored as a contact while count <= K, and with SVO_OVERLAP_ANY the walk
+ *    ends here.  Otherwise, at level 22 -- the depth limit of the guarded ray walk -- it sets flag bit 2
+ *    (overflow) and is not entered.  Otherwise it is entered.  The walk therefore ends on cyclic and
+ *    over-deep pools, and nothing about a pool needs validating.  Flag bit 0 is count > 0.
+ *  - Contact (svo_contact, 16 bytes): parent, meta = hit_idx | hit_scale << 8 and the voxel key have svo_hit's
+ *    and svo_frame.voxel's definitions for that voxel (hit_idx the slot, hit_scale 23 - level), so a contact
+ *    indexes the attachments exactly as a ray hit does.  Contacts come out in walk order, which is Morton
+ *    order.  Unused entries are {0xFFFFFFFF, 0, all ones}.
+ * One lane of a wave takes one shape, so one huge volume holds its wave for up to max_visits dependent
+ * fetches: that is what the budget is for.  Keep it small for broad-phase queries, and ask for a coarse_level
+ * when the leaves are not needed.
+ *
+ * svo_overlap_params is versioned by its size like svo_config: the caller sets `size` = sizeof as compiled;
+ * fields beyond it are 0.  NULL: all defaults.  root selects a subtree: 0 the terrain, or the root of a tree
+ * uploaded behind it (svo_set_buffer's dst_offset), the shape then given in that tree's own frame.  For a
+ * placed svo_object the sphere's centre is step 2 of the object rule applied to a point (q = c - p,
+ * c'_j = ((R_0j q_0 + R_1j q_1) + R_2j q_2) 2^-k) and the radius r 2^-k (overlap.py object_spheres); rotated
+ * boxes are out of scope, and so is a scene-wide form.
+ * Outputs (svo_overlap_out: device pointers, each nullable, not all NULL): every non-NULL output is fully
+ * written for all n -- summary n records, contacts n K entries (shape i's at i K), hitmask ceil(n / 64) words,
+ * bit i % 64 of word i / 64 = shape i touches a voxel, the unused bits of the last word 0.  Nothing is written
+ * past those.  n == 0: SVO_OK, nothing launched.  SVO_ERR_ARG, checked before any device is touched: a NULL
+ * context, shapes or out, an out with every pointer NULL; a size below 8 or above this library's; unknown
+ * flag bits; K > 32, contacts non-NULL with K == 0; max_visits > 2^24; coarse_level > 22; root >= the
+ * context's capacity; n > 2^31 - 1 or n K > 2^31 - 1; d_shapes, summary or contacts not 16-byte aligned, the
+ * mask not 8-byte aligned.  No pool uploaded: SVO_ERR_STATE.  A multi-device context runs the query on
+ * devices[0].  Asynchronous on `stream` (NULL: the context's own); the host form (no mask; summary and
+ * contacts nullable, not both NULL) blocks. */
+enum { SVO_SHAPE_BOX = 0, SVO_SHAPE_SPHERE = 1 };
+typedef struct svo_shape {      /* 32 bytes, 16-byte aligned in device memory */
+    float p[3];                 /* box: the low corner; sphere: the centre */
+    uint32_t kind;              /* SVO_SHAPE_BOX, SVO_SHAPE_SPHERE */
+    float q[3];                 /* box: the high corner; sphere: q[0] the radius, q[1] = q[2] = 0 */
+    uint32_t reserved;          /* 0 */
+} svo_shape;
+typedef struct svo_contact {    /* 16 bytes */
+    uint32_t parent;            /* descriptor holding the voxel; 0xFFFFFFFF = unused entry */
+    uint32_t meta;              /* hit_idx | hit_scale << 8 */
+    uint64_t key;               /* svo_frame.voxel's key; unused: all ones */
+} svo_contact;
+typedef struct svo_overlap {    /* 16 bytes: one shape's summary */
+    uint32_t count;             /* result voxels the shape touches (not capped by K) */
+    uint32_t visits;            /* descriptor fetches of its walk */
+    uint32_t flags;             /* bit0 count > 0, bit1 budget, bit2 overflow, bit4 invalid shape */
+    uint32_t reserved;          /* 0 */
+} svo_overlap;
+enum { SVO_OVERLAP_ANY = 1 };   /* svo_overlap_params.flags: stop at the first result voxel */
+enum { SVO_OVERLAP_MAX_CONTACTS = 32 };
+typedef struct svo_overlap_params {
+    uint32_t size;              /* sizeof(svo_overlap_params) as compiled by the caller */
+    uint32_t flags;             /* SVO_OVERLAP_ANY */
+    uint32_t root;              /* < capacity; 0 = the terrain */
+    uint32_t max_contacts;      /* K in 0..32 */
+    uint32_t max_visits;        /* 0: 65536; else 1..2^24 */
+    uint32_t coarse_level;      /* 0: none; else 1..22 */
+} svo_overlap_params;
+typedef struct svo_overlap_out {   /* device pointers, each nullable, not all NULL */
+    svo_overlap *summary;       /* n records */
+    svo_contact *contacts;      /* n K entries */
+    uint64_t *hitmask;          /* ceil(n/64) words */
+} svo_overlap_out;
+int svo_overlap_volumes(svo_ctx *ctx, const svo_shape *d_shapes, size_t n, const svo_overlap_params *params,
+                        const svo_overlap_out *out, void *stream);
+int svo_overlap_volumes_host(svo_ctx *ctx, const svo_shape *shapes, size_t n, const svo_overlap_params *params,
+                             svo_overlap *summary, svo_contact *contacts);
+
 /* Information about the uploaded pool. */
 int svo_get_info(svo_ctx *ctx, size_t *n_nodes, int *max_depth, int *device);
 

@@ -42,7 +42,8 @@ EXPORTS = ("svo_create", "svo_set_buffer", "svo_set_buffer_v2", "svo_set_camera"
            "svo_sample_sky_host", "svo_set_ambient", "svo_get_ambient", "svo_ambient_rays", "svo_ambient_rays_host",
            "svo_set_lights", "svo_get_lights", "svo_light_rays", "svo_light_rays_host",
            "svo_set_objects", "svo_get_objects", "svo_object_rays", "svo_object_rays_host", "svo_trace_scene",
-           "svo_trace_scene_host", "svo_scene_light_rays", "svo_scene_light_rays_host")
+           "svo_trace_scene_host", "svo_scene_light_rays", "svo_scene_light_rays_host",
+           "svo_overlap_volumes", "svo_overlap_volumes_host")
 # svo_ray: one caller-supplied ray of svo_trace_rays (world space, direction used as given)
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")])
 assert RAY_DTYPE.itemsize == 32
@@ -62,6 +63,14 @@ OBJECT_DTYPE = np.dtype([("root", "<u4"), ("scale_log2", "<i4"), ("flags", "<u4"
 assert OBJECT_DTYPE.itemsize == 64
 MAX_OBJECTS = 8                              # svo_set_objects / svo_trace_scene: at most 8 objects
 SCENE_NO_TERRAIN = 4                         # svo_trace_scene flags: the terrain (root 0) is no candidate
+# svo_shape / svo_contact / svo_overlap: one volume, one touched voxel and one summary of svo_overlap_volumes
+SHAPE_DTYPE = np.dtype([("p", "<f4", (3,)), ("kind", "<u4"), ("q", "<f4", (3,)), ("reserved", "<u4")])
+CONTACT_DTYPE = np.dtype([("parent", "<u4"), ("meta", "<u4"), ("key", "<u8")])
+OVERLAP_DTYPE = np.dtype([("count", "<u4"), ("visits", "<u4"), ("flags", "<u4"), ("reserved", "<u4")])
+assert SHAPE_DTYPE.itemsize == 32 and CONTACT_DTYPE.itemsize == 16 and OVERLAP_DTYPE.itemsize == 16
+SHAPE_BOX, SHAPE_SPHERE = 0, 1               # svo_shape.kind
+OVERLAP_ANY = 1                              # svo_overlap_params.flags: stop at the first result voxel
+OVERLAP_MAX_CONTACTS = 32
 SVO_OPT_SHADOW_RAYS = 1
 SVO_OPT_KERNEL_TIMING = 2
 SVO_OPT_COUNT_BEAM = 4
@@ -123,6 +132,22 @@ class SvoQueryOut(ctypes.Structure):
     """svo_query_out: device pointers (ints) of a ray query's outputs, each nullable."""
     _fields_ = [("hits", ctypes.c_void_p), ("position", ctypes.c_void_p), ("voxel", ctypes.c_void_p),
                 ("hitmask", ctypes.c_void_p)]
+
+
+class SvoOverlapParams(ctypes.Structure):
+    """svo_overlap_params, versioned by its size."""
+    _fields_ = [("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("root", ctypes.c_uint32),
+                ("max_contacts", ctypes.c_uint32), ("max_visits", ctypes.c_uint32), ("coarse_level", ctypes.c_uint32)]
+
+
+class SvoOverlapOut(ctypes.Structure):
+    """svo_overlap_out: device pointers (ints) of a volume query's outputs, each nullable."""
+    _fields_ = [("summary", ctypes.c_void_p), ("contacts", ctypes.c_void_p), ("hitmask", ctypes.c_void_p)]
+
+
+def overlap_params(root=0, max_contacts=0, any_hit=False, max_visits=0, coarse_level=0):
+    return SvoOverlapParams(ctypes.sizeof(SvoOverlapParams), OVERLAP_ANY if any_hit else 0, int(root), int(max_contacts),
+                            int(max_visits), int(coarse_level))
 
 
 # svo_config (include/svo_rt.h, ABI 10): the context's render policy, versioned by size
@@ -236,6 +261,8 @@ def lib():
         "svo_trace_scene_host": [vp, vp, sz, i, ctypes.c_uint32, vp, i, vp, vp, vp, vp],
         "svo_scene_light_rays": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp, i, vp, i, vp, vp],
         "svo_scene_light_rays_host": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp, i, vp, i, vp],
+        "svo_overlap_volumes": [vp, vp, sz, ctypes.POINTER(SvoOverlapParams), ctypes.POINTER(SvoOverlapOut), vp],
+        "svo_overlap_volumes_host": [vp, vp, sz, ctypes.POINTER(SvoOverlapParams), vp, vp],
         "svo_destroy": [vp],
         "svo_last_error": [],
         "svo_abi_version": [],

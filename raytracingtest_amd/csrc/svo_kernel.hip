@@ -2490,6 +2490,84 @@ __global__ __launch_bounds__(TILE) void scene_light_list_kernel(LaunchParams p, 
     if (mine) store_colour(p.out, le.i, res);
 }
 
+// ---------------------------------------------------------- volume queries
+// svo_overlap_volumes (svo_overlap.h is the rule and holds the walk itself): one lane per shape, one wave64
+// per 64 consecutive shapes -- query_rays_body's shape.  The walk's ancestor stack lives in LDS, [level][lane]
+// like the tracers' stack: per level {node, first} and the state word (nonleaf8 | pending slots << 8), 12
+// bytes per lane and level, so no register array is indexed at run time.  Lanes diverge: a wave lasts as
+// long as its largest volume, which max_visits bounds.  Invalid shapes and lanes past the list write their
+// outputs before the walk; the mask word is the ballot of the whole wave afterwards.
+static_assert(svo_volumes::MAX_LEVEL == S_MAX - 1 && svo_volumes::STACK_LEVELS == OBJECT_SLOTS,
+              "the overlap walk ends where the guarded ray walk's 21-slot stack does");
+
+struct OverlapFetch {
+    const uint2 *nodes;
+    uint32_t n_nodes;
+    __device__ __forceinline__ svo_volumes::Node operator()(uint32_t i) const {
+        const uint2 nd = i < n_nodes ? nodes[i] : make_uint2(0u, 0u);   // the guarded loop's fetch
+        return {nd.x & 0xFFFFu, nd.y};
+    }
+};
+
+struct OverlapStack {    // this lane's column of the two LDS arrays
+    uint2 *nf;
+    uint32_t *state;
+    __device__ __forceinline__ void push(int level, uint32_t node, uint32_t first, uint32_t st) {
+        nf[level * TILE] = make_uint2(node, first);
+        state[level * TILE] = st;
+    }
+    __device__ __forceinline__ void pop(int level, uint32_t &node, uint32_t &first, uint32_t &st) const {
+        const uint2 e = nf[level * TILE];
+        node = e.x;
+        first = e.y;
+        st = state[level * TILE];
+    }
+};
+
+struct OverlapSink {     // contact k of this lane's shape
+    uint4 *contacts;
+    __device__ __forceinline__ void operator()(uint32_t k, const svo_volumes::Contact &c) const {
+        contacts[k] = make_uint4(c.parent, c.meta, (uint32_t)c.key, (uint32_t)(c.key >> 32));
+    }
+};
+
+__global__ __launch_bounds__(TILE) void overlap_kernel(OverlapArgs a) {
+    __shared__ uint2 s_nf[svo_volumes::STACK_LEVELS * TILE];
+    __shared__ uint32_t s_state[svo_volumes::STACK_LEVELS * TILE];
+    const int lane = (int)threadIdx.x;
+    const uint32_t i = blockIdx.x * TILE + (uint32_t)lane;
+    const bool in = i < a.n;
+    svo_volumes::Shape s = {};
+    if (in) {   // two 16-byte loads
+        const float4 *src = reinterpret_cast<const float4 *>(a.shapes) + 2 * (size_t)i;
+        const float4 lo = src[0], hi = src[1];
+        s.p[0] = lo.x; s.p[1] = lo.y; s.p[2] = lo.z; s.kind = __float_as_uint(lo.w);
+        s.q[0] = hi.x; s.q[1] = hi.y; s.q[2] = hi.z;
+    }
+    const bool valid = in && svo_volumes::shape_valid(s);
+    const uint32_t k_max = a.contacts ? a.max_contacts : 0u;
+    uint4 *mine = reinterpret_cast<uint4 *>(a.contacts) + (size_t)i * k_max;
+    const uint4 unused = make_uint4(0xFFFFFFFFu, 0u, 0xFFFFFFFFu, 0xFFFFFFFFu);
+    if (in && !valid) {
+        if (a.summary) reinterpret_cast<uint4 *>(a.summary)[i] = make_uint4(0u, 0u, svo_volumes::FLAG_INVALID, 0u);
+        for (uint32_t k = 0; k < k_max; ++k) mine[k] = unused;
+    }
+    bool touch = false;
+    if (valid) {
+        OverlapFetch fetch{a.nodes, a.n_nodes};
+        OverlapStack stack{s_nf + lane, s_state + lane};
+        OverlapSink sink{mine};
+        const svo_volumes::Summary r =
+            svo_volumes::walk(s, a.root, a.flags, k_max, a.max_visits, a.coarse_level, fetch, stack, sink);
+        if (a.summary) reinterpret_cast<uint4 *>(a.summary)[i] = make_uint4(r.count, r.visits, r.flags, 0u);
+        for (uint32_t k = min(r.count, k_max); k < k_max; ++k) mine[k] = unused;
+        touch = r.count != 0u;
+    }
+    // lane 0 is always inside the list (the grid is ceil(n / 64) waves); lanes past it vote 0
+    const lmask m = LM_OF(touch);
+    if (lane == 0 && a.hitmask) a.hitmask[blockIdx.x] = m;
+}
+
 // ------------------------------------------------------------------ skybox
 // svo_set_skybox: the sky pass behind the primary launch.  One wave64 per 8x8 tile of the
 // launch's rows, in plain tile order (the pass has no heavy tiles to put first).  The tile's hit mask is
@@ -3806,6 +3884,15 @@ hipError_t launch_sample_sky(const svo_sky::Texture &sky, const float4 *dirs, ui
     if (!dirs || !out || (sky.texels && (sky.width <= 0 || sky.height <= 0))) return hipErrorInvalidValue;
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(sample_sky_kernel, dim3((n + 255u) / 256u), dim3(256), 0, stream, sky, dirs, n, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_overlap(const OverlapArgs &a, hipStream_t stream) {
+    if (!a.nodes || !a.shapes || a.max_contacts > svo_volumes::MAX_CONTACTS || a.max_visits == 0u ||
+        (!a.summary && !a.contacts && !a.hitmask))
+        return hipErrorInvalidValue;
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(overlap_kernel, dim3((a.n + (uint32_t)TILE - 1u) / (uint32_t)TILE), dim3(TILE), 0, stream, a);
     return hipGetLastError();
 }
 

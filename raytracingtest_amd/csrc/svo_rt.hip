@@ -2666,6 +2666,64 @@ int traced_host(svo_ctx *ctx, const char *name, const svo_ray *rays, size_t n, s
     });
 }
 
+// ---- volume queries (svo_overlap_volumes; svo_overlap.h is the rule)
+// The caller's params as this library reads them: the fields inside the caller's size, 0 beyond it; NULL: all
+// defaults.  max_visits comes out resolved (0: the default budget).
+int read_overlap_params(const svo_overlap_params *params, svo_overlap_params *k) {
+    std::memset(k, 0, sizeof *k);
+    if (params) {
+        if (params->size < 2 * sizeof(uint32_t)) return fail(SVO_ERR_ARG, "svo_overlap_params.size must hold at least size and flags");
+        if (params->size > sizeof *k)
+            return fail(SVO_ERR_ARG, "svo_overlap_params.size " + std::to_string(params->size) +
+                                         " is larger than this library's (" + std::to_string(sizeof *k) + "): a newer ABI");
+        std::memcpy(k, params, params->size);
+    }
+    k->size = sizeof *k;
+    if (k->flags & ~(uint32_t)SVO_OVERLAP_ANY) return fail(SVO_ERR_ARG, "unknown overlap flag bits");
+    if (k->max_contacts > svo_volumes::MAX_CONTACTS) return fail(SVO_ERR_ARG, "max_contacts must lie in 0..32");
+    if (k->max_visits > svo_volumes::MAX_VISITS) return fail(SVO_ERR_ARG, "max_visits must be 0 or lie in 1..2^24");
+    if (k->coarse_level > (uint32_t)svo_volumes::MAX_LEVEL) return fail(SVO_ERR_ARG, "coarse_level must be 0 or lie in 1..22");
+    if (k->max_visits == 0) k->max_visits = svo_volumes::DEFAULT_VISITS;
+    return SVO_OK;
+}
+
+// The checks the device and the host form share; out_error: the form's complaint about its outputs, or null.
+int check_overlap_args(svo_ctx *ctx, const void *shapes, size_t n, const svo_overlap_params *params, const char *out_error,
+                       bool has_contacts, svo_overlap_params *k) {
+    static_assert(sizeof(svo_shape) == sizeof(svo_volumes::Shape) && sizeof(svo_contact) == sizeof(svo_volumes::Contact) &&
+                      sizeof(svo_overlap) == sizeof(svo_volumes::Summary),
+                  "overlap record layouts");
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!shapes) return fail(SVO_ERR_ARG, "null shape list");
+    if (out_error) return fail(SVO_ERR_ARG, out_error);
+    if (int rc = read_overlap_params(params, k)) return rc;
+    if (has_contacts && k->max_contacts == 0) return fail(SVO_ERR_ARG, "contacts asked for with max_contacts 0");
+    if (int rc = check_batch_count(n, 1, "shapes")) return rc;
+    if (int rc = check_batch_count(n, std::max<size_t>(k->max_contacts, 1), "contacts")) return rc;
+    if ((size_t)k->root >= batch_context(ctx)->capacity) return fail(SVO_ERR_ARG, "root outside the node-pool capacity");
+    return SVO_OK;
+}
+
+// One volume query on context c (single-device), its device selected: arguments and pool checked by the caller.
+int overlap_device(svo_ctx *c, const svo_shape *d_shapes, size_t n, const svo_overlap_params &k, const svo_overlap_out &out,
+                   hipStream_t s) {
+    svo::OverlapArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.nodes = c->d_nodes;
+    a.n_nodes = (uint32_t)std::min<size_t>(c->n_nodes, 0xFFFFFFFFu);
+    a.shapes = reinterpret_cast<const svo_volumes::Shape *>(d_shapes);
+    a.n = (uint32_t)n;
+    a.flags = k.flags;
+    a.root = k.root;
+    a.max_contacts = k.max_contacts;
+    a.max_visits = k.max_visits;
+    a.coarse_level = k.coarse_level;
+    a.summary = reinterpret_cast<svo_volumes::Summary *>(out.summary);
+    a.contacts = reinterpret_cast<svo_volumes::Contact *>(out.contacts);
+    a.hitmask = reinterpret_cast<unsigned long long *>(out.hitmask);
+    return launched(svo::launch_overlap(a, s), "overlap launch");
+}
+
 }  // namespace
 
 extern "C" {
@@ -2842,6 +2900,43 @@ int svo_sample_sky_host(svo_ctx *ctx, const float *dirs, size_t n, float *rgba) 
         if (int rc = st.upload(p_dirs, dirs, 16 * n)) return rc;
         if (int rc = sky_launch(c, st.at(p_dirs), n, st.at(p_dirs), s)) return rc;
         if (int rc = st.download(rgba, p_dirs, 16 * n)) return rc;
+        return st.finish();
+    });
+}
+
+int svo_overlap_volumes(svo_ctx *ctx, const svo_shape *d_shapes, size_t n, const svo_overlap_params *params,
+                        const svo_overlap_out *out, void *stream) {
+    const char *out_error = !out ? "null svo_overlap_out"
+                            : !out->summary && !out->contacts && !out->hitmask ? "every overlap output is null"
+                                                                               : nullptr;
+    svo_overlap_params k;
+    if (int rc = check_overlap_args(ctx, d_shapes, n, params, out_error, out && out->contacts, &k)) return rc;
+    if (((uintptr_t)d_shapes | (uintptr_t)out->summary | (uintptr_t)out->contacts) & 15u)
+        return fail(SVO_ERR_ARG, "shapes, summaries and contacts must be 16-byte aligned");
+    if ((uintptr_t)out->hitmask & 7u) return fail(SVO_ERR_ARG, "the hit mask must be 8-byte aligned");
+    if (n == 0) return SVO_OK;
+    return on_device(ctx, "svo_overlap_volumes", stream, true,
+                     [&](svo_ctx *c, hipStream_t s) { return overlap_device(c, d_shapes, n, k, *out, s); });
+}
+
+int svo_overlap_volumes_host(svo_ctx *ctx, const svo_shape *shapes, size_t n, const svo_overlap_params *params,
+                             svo_overlap *summary, svo_contact *contacts) {
+    const char *out_error = !summary && !contacts ? "every overlap output is null" : nullptr;
+    svo_overlap_params k;
+    if (int rc = check_overlap_args(ctx, shapes, n, params, out_error, contacts != nullptr, &k)) return rc;
+    if (n == 0) return SVO_OK;
+    return on_device(ctx, "svo_overlap_volumes_host", nullptr, true, [&](svo_ctx *c, hipStream_t s) {
+        HostStage st(c);
+        const size_t n_contacts = contacts ? n * k.max_contacts : 0;
+        const size_t p_shapes = st.part(32 * n), p_sum = st.part(summary ? 16 * n : 0), p_con = st.part(16 * n_contacts);
+        if (int rc = st.begin()) return rc;
+        if (int rc = st.upload(p_shapes, shapes, 32 * n)) return rc;
+        svo_overlap_out out{};
+        out.summary = st.at_if<svo_overlap>(summary, p_sum);
+        out.contacts = st.at_if<svo_contact>(contacts, p_con);
+        if (int rc = overlap_device(c, st.at<const svo_shape>(p_shapes), n, k, out, s)) return rc;
+        if (int rc = st.download(summary, p_sum, 16 * n)) return rc;
+        if (int rc = st.download(contacts, p_con, 16 * n_contacts)) return rc;
         return st.finish();
     });
 }

@@ -15,6 +15,7 @@
 
 #include "svo_light.h"
 #include "svo_object.h"
+#include "svo_overlap.h"
 #include "svo_sky.h"
 
 namespace svo {
@@ -402,5 +403,25 @@ hipError_t launch_scene_shadows(const LaunchParams &p, void *scratch, const svo_
                                 int stack_mode, hipStream_t stream);
 hipError_t launch_scene_lights(const LaunchParams &p, const LightArgs &la, const svo_objects::Object *objects, int n_objects,
                                const uint8_t *ids, int stack_mode, hipStream_t stream);
+
+// Volume queries (svo_overlap_volumes; svo_kernel.hip overlap_kernel, svo_overlap.h is the rule and the walk):
+// one lane per shape, one wave64 per 64 consecutive shapes.  Every non-null output is fully written for all n:
+// summary n records, contacts n * max_contacts entries (unused ones {0xFFFFFFFF, 0, all ones}), hitmask
+// ceil(n / 64) words with the tail bits 0.  Reads the node pool only.
+struct OverlapArgs {
+    const uint2 *nodes;
+    uint32_t n_nodes;                     // fetches at or past it read the zero descriptor
+    const svo_volumes::Shape *shapes;     // 16-byte aligned
+    uint32_t n;                           // shapes (<= 2^31 - 1; n * max_contacts too)
+    uint32_t flags;                       // svo_volumes::ANY
+    uint32_t root;
+    uint32_t max_contacts;                // 0 .. 32
+    uint32_t max_visits;                  // resolved: 1 .. 2^24
+    uint32_t coarse_level;                // 0: none
+    svo_volumes::Summary *summary;        // 16-byte aligned, like contacts
+    svo_volumes::Contact *contacts;
+    unsigned long long *hitmask;
+};
+hipError_t launch_overlap(const OverlapArgs &a, hipStream_t stream);
 
 }  // namespace svo

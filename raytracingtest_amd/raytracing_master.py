@@ -21,6 +21,8 @@ Beyond the reference (one GPU, one Dispatch):
                                  of the one-process-per-GPU split)
   TraceRays(origins, dirs)       caller-supplied ray batches (the reference's CPU-side
   trace_rays_device(...)         SVO.Trace(Ray), Interfaces.cs:6-15) on the GPU
+  OverlapVolumes(shapes)         which voxels boxes and spheres touch (no reference counterpart)
+  overlap_volumes_device(...)
 Errors surface as SvoError (the C-ABI status + svo_last_error text) instead of
 Unity's silent shader failures.  There is no CPU fallback.
 """
@@ -705,6 +707,36 @@ class RaytracingMaster:
         check(_lib.lib().svo_scene_light_rays(self._ctx, rays_ptr, int(n), self._query_flags(False, raw), hits, voxel,
                                               object_id, obs.ctypes.data if len(obs) else None, len(obs),
                                               rec.ctypes.data, len(rec), out, stream), "svo_scene_light_rays")
+
+    # --------------------------------------------------------- volume queries
+    def OverlapVolumes(self, shapes, root=0, max_contacts=0, any_hit=False, max_visits=0, coarse_level=0):
+        """Which voxels do these volumes touch (svo_overlap_volumes_host; overlap.overlap_model is its Python
+        statement)?  shapes: svo_shape records (overlap.make_boxes / make_spheres), world space, or the frame of
+        the tree at `root` (0: the terrain; a placed object: overlap.object_spheres).  max_contacts: K in
+        0..32 contact records per shape; any_hit: stop at the first touched voxel; max_visits: the walk's budget
+        of descriptor fetches (0: 65536) -- one lane of a wave walks one shape, so one huge volume holds its
+        wave that long; coarse_level: report the voxels of that level instead of descending further.  Blocking.
+        Returns the summaries (OVERLAP_DTYPE [n]: count, visits, flags -- bit 0 touches, 1 budget, 2 overflow,
+        0x10 invalid shape), or (summaries, contacts [n, K] CONTACT_DTYPE) with max_contacts > 0."""
+        shapes = np.ascontiguousarray(shapes, _lib.SHAPE_DTYPE).reshape(-1)
+        n = len(shapes)
+        prm = _lib.overlap_params(root, max_contacts, any_hit, max_visits, coarse_level)
+        summary = np.zeros(n, _lib.OVERLAP_DTYPE)
+        contacts = np.zeros((n, int(max_contacts)), _lib.CONTACT_DTYPE) if max_contacts else None
+        check(_lib.lib().svo_overlap_volumes_host(self._ctx, shapes.ctypes.data, n, ctypes.byref(prm), summary.ctypes.data,
+                                                  None if contacts is None else contacts.ctypes.data),
+              "svo_overlap_volumes_host")
+        return summary if contacts is None else (summary, contacts)
+
+    def overlap_volumes_device(self, shapes_ptr, n, summary=None, contacts=None, hitmask=None, root=0, max_contacts=0,
+                               any_hit=False, max_visits=0, coarse_level=0, stream=None):
+        """Asynchronous svo_overlap_volumes on device buffers: shapes_ptr = n svo_shape records (32 bytes each,
+        16-byte aligned); summary (n x 16 bytes), contacts (n x max_contacts x 16 bytes) and hitmask
+        (ceil(n / 64) uint64) are raw device pointers, each nullable, and are fully written."""
+        prm = _lib.overlap_params(root, max_contacts, any_hit, max_visits, coarse_level)
+        out = _lib.SvoOverlapOut(summary, contacts, hitmask)
+        check(_lib.lib().svo_overlap_volumes(self._ctx, shapes_ptr, int(n), ctypes.byref(prm), ctypes.byref(out), stream),
+              "svo_overlap_volumes")
 
     def beam_starts_device(self, width, height, starts_ptr, band=None, stream=None):
         """svo_beam_starts: every primary ray's beam start (SVO-space t, -inf: the cube entry) into a

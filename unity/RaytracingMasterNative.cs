@@ -174,6 +174,39 @@ public static class SvoNative {
     [DllImport(Lib)] public static extern int svo_get_skybox(IntPtr ctx, out int width, out int height, out uint flags);
     [DllImport(Lib)] public static extern int svo_sample_sky(IntPtr ctx, IntPtr dDirs, UIntPtr n, IntPtr dRgba, IntPtr stream);
     [DllImport(Lib)] public static extern int svo_sample_sky_host(IntPtr ctx, [In] Vector4[] dirs, UIntPtr n, [Out] Color[] rgba);
+    // Volume queries (svo_rt.h): which voxels a world-space box or sphere touches.  svo_shape: 32 bytes, the
+    // header's field order; the frame is the tree's own world convention, the cube [-16, 16]^3.
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoShape {
+        public float pX, pY, pZ;                  // box: the low corner; sphere: the centre
+        public uint kind;                         // ShapeBox, ShapeSphere
+        public float qX, qY, qZ;                  // box: the high corner; sphere: qX the radius, qY = qZ = 0
+        public uint reserved;                     // 0
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoContact {                    // == svo_contact, 16 bytes
+        public uint parent;                       // descriptor holding the voxel; 0xFFFFFFFF: unused entry
+        public uint meta;                         // hit_idx | hit_scale << 8
+        public ulong key;                         // the voxel key of a ray hit
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoOverlap {                    // == svo_overlap, 16 bytes
+        public uint count, visits, flags, reserved;   // flags: bit0 touches, bit1 budget, bit2 overflow, 0x10 invalid shape
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoOverlapParams {              // == svo_overlap_params, versioned by size
+        public uint size, flags, root, maxContacts, maxVisits, coarseLevel;
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoOverlapOut { public IntPtr summary, contacts, hitmask; }   // device pointers
+    public const uint ShapeBox = 0, ShapeSphere = 1, OverlapAny = 1;
+    public const int OverlapMaxContacts = 32;
+    [DllImport(Lib)] public static extern int svo_overlap_volumes(IntPtr ctx, IntPtr dShapes, UIntPtr n,
+                                                                  ref SvoOverlapParams prm, ref SvoOverlapOut output,
+                                                                  IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_overlap_volumes_host(IntPtr ctx, [In] SvoShape[] shapes, UIntPtr n,
+                                                                       ref SvoOverlapParams prm, [Out] SvoOverlap[] summary,
+                                                                       [Out] SvoContact[] contacts);
 
     [StructLayout(LayoutKind.Sequential)]
     public struct SvobResult {   // == svob_result
@@ -335,6 +368,28 @@ public class RaytracingMasterNative : MonoBehaviour {
             points[i] = rays[i].GetPoint(hits[i].t / 64.0f);   // world hit point = origin + (t / 64) dir
             n++;
         }
+        return n;
+    }
+
+    // Which voxels do these volumes touch (svo_overlap_volumes_host)?  Collision broad-phase, spawn placement,
+    // trigger volumes.  Shapes in world space (SvoNative.SvoShape: a box or a sphere); root 0 is the terrain.
+    // maxContacts: 0..32 contact records per shape (contacts[i * maxContacts ..], Morton order; null with 0);
+    // anyHit: stop at the first voxel; maxVisits: the walk's budget of descriptor fetches (0: 65536) -- one GPU
+    // lane walks one shape, so keep huge volumes on a small budget or a coarseLevel.  Returns how many touch.
+    public int OverlapVolumes(SvoNative.SvoShape[] shapes, out SvoNative.SvoOverlap[] summary,
+                              out SvoNative.SvoContact[] contacts, uint root = 0, int maxContacts = 0, bool anyHit = false,
+                              uint maxVisits = 0, uint coarseLevel = 0) {
+        summary = new SvoNative.SvoOverlap[shapes.Length];
+        contacts = maxContacts > 0 ? new SvoNative.SvoContact[shapes.Length * maxContacts] : null;
+        if (shapes.Length == 0) return 0;
+        var prm = new SvoNative.SvoOverlapParams {
+            size = (uint)Marshal.SizeOf(typeof(SvoNative.SvoOverlapParams)), flags = anyHit ? SvoNative.OverlapAny : 0u,
+            root = root, maxContacts = (uint)maxContacts, maxVisits = maxVisits, coarseLevel = coarseLevel };
+        SvoNative.Check(SvoNative.svo_overlap_volumes_host(_ctx, shapes, (UIntPtr)shapes.Length, ref prm, summary, contacts),
+                        "svo_overlap_volumes_host");
+        int n = 0;
+        for (int i = 0; i < summary.Length; i++)
+            if ((summary[i].flags & 1) != 0) n++;
         return n;
     }
 
