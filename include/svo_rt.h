@@ -543,7 +543,8 @@ int svo_trace_rays_lod_host(svo_ctx *ctx, const svo_ray *rays, size_t n_rays, in
  *  5. the bounce ray is {origin, t_max +inf, r, 0}, traced as svo_trace_rays traces it with flags 0.
  * Deviation (documented): the reference's origin P + 0.001 n uses the smooth normal, which on voxels
  * very often lies on or inside the voxel just hit (INTEGRATION.md "Reflections" has the counts);
- * here the ray leaves through the cube face it entered by and cannot re-enter that voxel.
+ * here the ray leaves through the cube face it entered by and, on pools of up to 12 levels, cannot
+ * re-enter that voxel; from 16 levels on some rays do (INTEGRATION.md "Reflections", the table by depth).
  *
  * svo_bounce_rays: from a batch and its results to the next batch: out[i] = the bounce ray of
  * rays[i] if hits[i] has flag bit 0, else the dead ray (all 32 bytes zero except t_max = +inf: a

@@ -5,7 +5,10 @@
 //
 // Deviation from the reference (documented): the reference has no ambient term.  The rays are distributed
 // about the normal of the entry face, not the smooth normal: a ray's direction is then a permutation of a
-// table entry with one sign, and no hemisphere ray can re-enter the voxel it left.
+// table entry with one sign, and in real arithmetic no hemisphere ray can re-enter the voxel it left.  In f32
+// that is derived for pools of up to 12 levels and ends where the bounce origin's promise ends (svo_reflect.h):
+// with N = 4 no ray re-entered through 16 levels, 162 of 32,256 did at 17 and 6,884 of 32,008 at 18
+// (DESIGN.md 3.2c, 3.2e).  A ray that re-enters counts as occluded.
 #pragma once
 
 #include <cstdint>

@@ -8,6 +8,14 @@
 // voxel just hit, and the bounce ray hits it again at t ~ 0.  Here the ray leaves through the cube
 // face it entered by, and its direction is mirrored on that face when the smooth normal would send
 // it back in.
+//
+// Where that holds: the origin stands side 2^-6 = 2^-(L + 6) SVO units off the face of a level-L voxel
+// (hit_scale = 23 - L).  The addition to face_g is exact down to hit_scale 4; what the step must survive
+// is the query's world -> SVO transform o' = fl(o / 32 + 1.5), spaced 2^-23 SVO units (the step is 4, 2,
+// 1 and 1/2 of that at 15, 16, 17 and 18 levels), and the walk's plane rounding of up to
+// 10 * 2^-23 max(1, |o'|).  Through 12 levels the step exceeds both and no ray of this origin can re-enter
+// the voxel it left; none was observed through 15 levels; from 16 levels on some do (DESIGN.md 3.2c has
+// the counts by depth, tests/secondary_geometry_model.py the float64 model they come from).
 #pragma once
 
 #include <cmath>

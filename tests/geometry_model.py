@@ -67,7 +67,9 @@ HLSL_REL = 2.0 ** -17
 EXACT, HLSL = 1, 0                      # svo_stack_mode values
 FLAG_HIT, FLAG_CAP, FLAG_OVERFLOW = 1, 2, 4
 WALK_DEPTHS = (7, 12, 16, 19, 21)
-POOLS = ("walk7", "menger7", "walk12", "mixed", "walk16", "walk19", "walk21")
+# walk14 .. walk18: the secondary-ray tests' depths (tests/secondary_geometry_model.py); appended, because
+# family_rays seeds by a pool's index here
+POOLS = ("walk7", "menger7", "walk12", "mixed", "walk16", "walk19", "walk21", "walk14", "walk15", "walk17", "walk18")
 FAMILIES = ("far", "near", "mid", "surface", "slanted", "camera")
 DECIDED_FLOOR = {"walk7": 0.99, "menger7": 0.99, "walk12": 0.95, "mixed": 0.95, "walk16": 0.40}
 CAM_W, CAM_H = 128, 96
@@ -480,12 +482,15 @@ def check(name, traced, mode, summary, hits, voxel, what=""):
     return check_of(pool(name)[1], *svo_rays(traced), mode, summary, hits, voxel, what=what)
 
 
-def check_of(leaves, o, d, m, mode, summary, hits, voxel, what=""):
+def check_of(leaves, o, d, m, mode, summary, hits, voxel, what="", t_lim=None, skip=None, masks=None):
     """Section-2 assertions on any tracer's hit records and voxel keys.  Returns the figures for the
     record: rays, hits, decided share, max_gap_ulp -- the largest distance of a reported voxel from the
     float64 ray in units of 2^-23 (the margin allows K max(1, |o'|_inf) of them) -- and max_entry_dev,
     the largest deviation of t from the leaf's entry in units of 2^-23 max(1, |o'|_inf) / min |d_k| (K allowed).
-    leaves, o, d, m: as model_of takes them."""
+    leaves, o, d, m: as model_of takes them, t_lim and skip too (the summary was made with them).  A record that
+    reports its ray's skipped leaf -- the voxel a secondary ray starts on -- is a self-hit: its key and scale are
+    checked, it is counted (self_hits, and empty_but_hit where the ray's may set is empty) and otherwise left
+    alone.  masks: a dict that receives self_hit [n] and rows [n] (the reported leaf rows, -1 on misses)."""
     voxel = np.asarray(voxel, np.uint64)
     flags = hits["flags"]
     assert not np.any(flags & (FLAG_CAP | FLAG_OVERFLOW)), f"{what}: iteration-cap or overflow flag"
@@ -497,28 +502,41 @@ def check_of(leaves, o, d, m, mode, summary, hits, voxel, what=""):
         rows = leaf_rows_of(leaves, hits[h])
     except AssertionError as e:
         raise AssertionError(f"{what}: {e}") from None
-    p = pairs_of(leaves, rows, o[h], d[h], m[h])
-    assert p["may"].all(), f"{what}: {np.count_nonzero(~p['may'])} reported voxels off the ray, first rays {h[~p['may']][:5]}"
+    own = np.zeros(len(h), bool) if skip is None else rows == np.asarray(skip)[h]
+    ok = ~own
+    p = pairs_of(leaves, rows, o[h], d[h], m[h], t_lim=None if t_lim is None else np.asarray(t_lim, np.float64)[h])
+    off = ok & ~p["may"]
+    assert not off.any(), f"{what}: {np.count_nonzero(off)} reported voxels off the ray, first rays {h[off][:5]}"
     assert np.array_equal(hits["hit_scale"][h], 23 - leaves[rows, 2]), f"{what}: hit_scale != 23 - L"
     assert np.array_equal(voxel[h], voxel_keys(leaves[rows])), f"{what}: voxel key"
     assert np.all(voxel[~hit] == ~np.uint64(0)) and np.all(np.isinf(hits["t"][~hit])), f"{what}: a miss carries a key or a t"
     t = hits["t"][h].astype(np.float64) / 2048.0
     tol = m[h] / np.abs(d[h]).min(axis=1)
     dev = np.abs(t - p["entry_true"])
-    bad = dev > tol
+    bad = ok & (dev > tol)
     assert not bad.any(), f"{what}: {bad.sum()} entry distances off, worst {np.max(dev / tol):.2f} tolerances (ray {h[np.argmax(dev / tol)]})"
-    late = p["entry_g"] > summary["must_entry"][h] + summary["must_slack"][h]
+    late = ok & (p["entry_g"] > summary["must_entry"][h] + summary["must_slack"][h])
     assert not late.any(), f"{what}: {late.sum()} rays report a voxel behind a must leaf, first {h[late][:5]}"
     lost = (summary["n_must"] > 0) & ~hit
     assert not lost.any(), f"{what}: {lost.sum()} rays with a must leaf came back as misses, first {np.flatnonzero(lost)[:5]}"
-    ghost = (summary["n_may"] == 0) & (hit | (flags != 0))
-    assert not ghost.any(), f"{what}: {ghost.sum()} rays with an empty may set are no plain miss"
-    wrong = summary["decided"][h] & (rows != summary["first"][h])
+    self_hit = np.zeros(len(hits), bool)
+    self_hit[h] = own
+    ghost = ~self_hit & (summary["n_may"] == 0) & (hit | (flags != 0))
+    assert not ghost.any(), f"{what}: {ghost.sum()} rays with an empty may set are no plain miss, first {np.flatnonzero(ghost)[:5]}"
+    wrong = ok & summary["decided"][h] & (rows != summary["first"][h])
     assert not wrong.any(), f"{what}: {wrong.sum()} decided rays report another leaf, first {h[wrong][:5]}"
-    return {"rays": int(len(hits)), "hits": int(hit.sum()), "must": int((summary["n_must"] > 0).sum()),
-            "model_misses": int((summary["n_may"] == 0).sum()), "decided_share": round(decided_share([summary]), 4),
-            "max_gap_ulp": round(float(np.max(p["gap"] / ULP)), 3) if len(h) else 0.0,
-            "max_entry_dev": round(float(np.max(dev / tol) * K), 3) if len(h) else 0.0}
+    fig = {"rays": int(len(hits)), "hits": int(hit.sum()), "must": int((summary["n_must"] > 0).sum()),
+           "model_misses": int((summary["n_may"] == 0).sum()),
+           "decided_share": round(decided_share([summary]), 4) if (summary["n_may"] > 0).any() else 1.0,
+           "max_gap_ulp": round(float(np.max(p["gap"][ok] / ULP)), 3) if ok.any() else 0.0,
+           "max_entry_dev": round(float(np.max((dev / tol)[ok]) * K), 3) if ok.any() else 0.0}
+    if skip is not None:
+        fig.update(self_hits=int(own.sum()), empty_but_hit=int((self_hit & (summary["n_may"] == 0)).sum()))
+    if masks is not None:
+        full = np.full(len(hits), -1, np.int64)
+        full[h] = rows
+        masks.update(self_hit=self_hit, rows=full)
+    return fig
 
 
 # --------------------------------------------------------------------------------- shadow rays

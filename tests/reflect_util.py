@@ -6,6 +6,7 @@ bounce ray, reflection.bounce_rays for the rule, and the fold res += e * col in 
 A frame's paths do not depend on the specular setting (unless it is all zero), so the bounce generations
 of a frame are traced once (generations) and folded per setting (expected_frame)."""
 import ctypes
+import functools
 
 import numpy as np
 
@@ -20,6 +21,15 @@ from tests.split_cases import edge_camera
 CAMS = {"main": main_camera, "overview": overview_camera}
 # diagonal: the guarded pools' camera (tests/guard_pools.py); edge: the split tests' (tests/split_cases.py)
 POSES = dict(CAMS, diagonal=diagonal_camera, edge=edge_camera)
+
+
+def _geometry_camera(name):
+    from tests import geometry_model
+    return geometry_model.camera(name)
+
+
+# geometry_<pool>: geometry_model.camera's view of one of its pools (tests/test_gpu_secondary_geometry.py)
+POSES.update({f"geometry_{n}": functools.partial(_geometry_camera, n) for n in ("walk12", "walk16")})
 SIZES = {"raster": (200, 120), "strips": (256, 128)}   # 25 tile columns: the raster path; 32: XCD strips
 DEFAULT = ((0.5, 0.25, 0.75), 7)
 SECOND = ((1.0, 0.0, 0.0), 2)

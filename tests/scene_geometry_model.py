@@ -674,6 +674,7 @@ def float64_origins(set_name, rays, hits, ids):
     last term the bound of test_world_origin_within_four_ulp_of_float64 on the step Q' -> Q.
     ambiguous: the two latest slab entries lie closer than their own uncertainty m / |d'_g| + m / |d'_h|, so f32
     may enter through the other face; such records have no single float64 origin and are counted, not checked."""
+    from tests.scene_geometry_util import entered_face_point      # that module imports this one
     ids = np.asarray(ids, np.int64)
     n = len(ids)
     rows = record_rows(set_name, hits, ids)
@@ -688,17 +689,11 @@ def float64_origins(set_name, rays, hits, ids):
         _, k, p, R = cd
         leaves = pools()[cd[0]][1][rows[at]]
         o2, d2, m, _ = frame(cd, o[at], d[at])
-        lo, hi, side = gm.boxes(leaves)
-        tn = np.fmin((lo - o2) / d2, (hi - o2) / d2)
-        order = np.argsort(tn, axis=1)
+        e = entered_face_point(leaves, o2, d2, m)
         r = np.arange(len(at))
-        g, h2 = order[:, 2], order[:, 1]
         ad = np.abs(d2)
-        amb[at] = tn[r, g] - tn[r, h2] <= m / ad[r, g] + m / ad[r, h2]
-        te = np.maximum(tn[r, g], 0.0)
-        q = o2 + te[:, None] * d2
-        out = -np.sign(d2[r, g])
-        q[r, g] = np.where(d2[r, g] > 0, lo[r, g], hi[r, g]) + out * side * 2.0 ** -6
+        g, out, te, q = e["g"], e["out"], e["te"], e["q"]
+        amb[at] = e["ambiguous"]
         Q[at] = to_world(cd, q)
         nf = np.zeros((len(at), 3))
         nf[r, g] = out

@@ -69,6 +69,31 @@ def check_shadow_classes(fig, what):
         assert fig[k] >= CLASS_FLOOR, f"{what}: {fig[k]} pixels of class {k}"
 
 
+# ------------------------------------------------------------------- the entered face, float64
+def entered_face_point(leaf_rows, o2, d2, m):
+    """Where a float64 frame ray (o2, d2 [n, 3], SVO units; margin m [n]) enters its leaf (leaf_rows [n]: rows of
+    SVOData.leaf_voxels()), and the origin of a secondary ray there: the entry point with its coordinate on the
+    entered axis set to the face plus 2^-6 of the voxel's side outward (reflection.entry_face's step 3; dyadic,
+    exact).  Shared by scene_geometry_model.float64_origins and tests/secondary_geometry_model.py.  Returns a dict
+    of [n] arrays: q [n, 3] that origin, g the entered axis (the slab the ray enters last), out = -sign(d2_g),
+    te the entry parameter (clamped at 0), face the entered face's coordinate, side, and ambiguous: the two latest
+    slab entries lie closer than their own uncertainty m / |d_g| + m / |d_h|, so f32 may enter through the other
+    face."""
+    lo, hi, side = gm.boxes(leaf_rows)
+    tn = np.fmin((lo - o2) / d2, (hi - o2) / d2)
+    order = np.argsort(tn, axis=1)
+    r = np.arange(len(o2))
+    g, h2 = order[:, 2], order[:, 1]
+    ad = np.abs(d2)
+    amb = tn[r, g] - tn[r, h2] <= m / ad[r, g] + m / ad[r, h2]
+    te = np.maximum(tn[r, g], 0.0)
+    q = o2 + te[:, None] * d2
+    out = -np.sign(d2[r, g])
+    face = np.where(d2[r, g] > 0, lo[r, g], hi[r, g])
+    q[r, g] = face + out * side * 2.0 ** -6
+    return {"q": q, "g": g, "out": out, "te": te, "face": face, "side": side, "ambiguous": amb}
+
+
 # -------------------------------------------------------------------------------- point lights
 def light_segments_check(rays, hits, ids, segments, trace, mode, what):
     """The query route of the point lights: `segments` = the scene-light rays of a scene query's records (rays,
