@@ -1020,6 +1020,79 @@ int svo_overlap_volumes(svo_ctx *ctx, const svo_shape *d_shapes, size_t n, const
 int svo_overlap_volumes_host(svo_ctx *ctx, const svo_shape *shapes, size_t n, const svo_overlap_params *params,
                              svo_overlap *summary, svo_contact *contacts);
 
+/* Closest voxels: how far is this point from the surface, and where is the closest point on it?  Pushing a
+ * sphere out of the terrain, conservative advancement of a moving sphere (step by distance - r), particle and
+ * cloth collision, snap-to-surface, clearance tests, distance-field slices.  The reference has no such query
+ * (a documented addition, like the volume queries).  A batch of caller-supplied points, each with a search
+ * radius; per point the nearest result voxel, its squared distance, the closest point on it, its contact
+ * record and one bit of a hit mask.  The query reads the node pool only and leaves every piece of render
+ * state alone, like svo_overlap_volumes.
+ *
+ * The closest-voxel rule (csrc/svo_closest.h, which carries the proofs; Python: closest.py; INTEGRATION.md
+ * "Closest voxels").  Exact: the pruned walk returns the voxel a brute force over all result voxels returns
+ * under the same f32 expression, byte for byte.  Every operation is one IEEE f32 rounding, no fma, only + - *,
+ * compares and selects; no sqrt, no division: the query reports d2 and the caller takes the root.
+ *  - Query: an svo_shape of kind SVO_SHAPE_SPHERE, centre p the point, q[0] the search radius.  INVALID under
+ *    svo_overlap_volumes' rule for shapes, and also when its kind is SVO_SHAPE_BOX.  An invalid query is not
+ *    walked: flags 0x10, visits 0, nothing found, mask bit 0.  r2 = q[0] q[0]; with SVO_CLOSEST_UNBOUNDED the
+ *    radius is ignored and r2 = +inf (the radius must still be valid).
+ *  - Frame, voxel boxes, slots and the child descriptor index are the volume queries'.
+ *  - Distance to a voxel box [lo, hi]: e_k = max(max(lo_k - p_k, p_k - hi_k), 0), d2 = (e0 e0 + e1 e1) + e2 e2
+ *    -- the sphere touch test's expression, so a voxel is a candidate iff d2 <= r2 and "found" equals
+ *    svo_overlap_volumes' touch bit for the same shape.
+ *  - Result voxels are the overlap walk's: a valid child whose non-leaf bit is clear, or whose level equals
+ *    coarse_level (when non-zero); a non-leaf child at level 22 sets flag bit 2 (overflow) and is not entered.
+ *  - Answer: the result voxel with the smallest (d2, Morton position).  Morton position: with the aligned
+ *    coordinates a_k = i_k << (22 - level), A precedes B iff, on the axis whose a_k ^ b_k has the highest set
+ *    bit (bit positions tying: z before y before x), A's coordinate is smaller -- the order in which
+ *    svo_overlap_volumes reports disjoint voxels.
+ *  - Walk: depth-first from `root`.  bound starts at r2 and becomes the best d2 once a result voxel is found;
+ *    the best is replaced iff the new d2 is smaller, or equal and Morton-earlier.  At a descriptor the pending
+ *    children are the valid ones; repeatedly the pending child with the smallest (d2_c, slot c) among those
+ *    with d2_c <= bound, the bound of that moment, is taken.  `visits` counts descriptor fetches; an index at
+ *    or past the uploaded nodes reads the zero descriptor.  A fetch that would make visits exceed max_visits
+ *    sets flag bit 1 (budget) and ends the walk with the best so far, which may then not be the nearest.  The
+ *    walk ends on cyclic and over-deep pools.
+ *  - Closest point: c_k = min(max(p_k, lo_k), hi_k), exact.  d2 == 0: the point lies in or on the voxel.
+ *  - Against real arithmetic (no e_k e_k under- or overflowing): d2, and the true squared distance of the
+ *    answer, are within a relative 11 * 2^-24 of the true minimum over all result voxels.
+ * svo_closest_params is versioned by its size like svo_overlap_params; NULL: all defaults.  root selects a
+ * tree as in svo_overlap_volumes; for a placed svo_object move the point as closest.py object_queries does.
+ * Outputs (svo_closest_out: device pointers, each nullable, not all NULL): every non-NULL output is fully
+ * written for all n -- nearest n records, contacts n entries (the answer's svo_contact; nothing found:
+ * {0xFFFFFFFF, 0, all ones}), hitmask ceil(n / 64) words, bit i % 64 of word i / 64 = query i found a voxel,
+ * the unused bits of the last word 0.  Nothing is written past those.  n == 0: SVO_OK, nothing launched.
+ * SVO_ERR_ARG, checked before any device is touched: a NULL context, queries or out, an out with every pointer
+ * NULL; a size below 8 or above this library's; unknown flag bits; max_visits > 2^24; coarse_level > 22;
+ * root >= the context's capacity; n > 2^31 - 1; d_queries, nearest or contacts not 16-byte aligned, the mask
+ * not 8-byte aligned.  No pool uploaded: SVO_ERR_STATE.  A multi-device context runs the query on devices[0].
+ * Asynchronous on `stream` (NULL: the context's own); the host form (no mask; nearest and contacts nullable,
+ * not both NULL) blocks. */
+enum { SVO_CLOSEST_UNBOUNDED = 1 };   /* svo_closest_params.flags: ignore the search radius */
+typedef struct svo_closest {    /* 32 bytes, 16-byte aligned in device memory */
+    float point[3];             /* closest point on the voxel's closed box; not found: 0, 0, 0 */
+    float d2;                   /* squared distance by the rule; not found: +inf */
+    uint32_t parent, meta;      /* as svo_contact; not found: 0xFFFFFFFF, 0 */
+    uint32_t visits;            /* descriptor fetches of the walk */
+    uint32_t flags;             /* bit0 found, bit1 budget, bit2 overflow, bit4 invalid query */
+} svo_closest;
+typedef struct svo_closest_params {
+    uint32_t size;              /* sizeof(svo_closest_params) as compiled by the caller */
+    uint32_t flags;             /* SVO_CLOSEST_UNBOUNDED */
+    uint32_t root;              /* < capacity; 0 = the terrain */
+    uint32_t max_visits;        /* 0: 65536; else 1..2^24 */
+    uint32_t coarse_level;      /* 0: none; else 1..22 */
+} svo_closest_params;
+typedef struct svo_closest_out {   /* device pointers, each nullable, not all NULL */
+    svo_closest *nearest;       /* n records */
+    svo_contact *contacts;      /* n entries */
+    uint64_t *hitmask;          /* ceil(n/64) words */
+} svo_closest_out;
+int svo_closest_voxels(svo_ctx *ctx, const svo_shape *d_queries, size_t n, const svo_closest_params *params,
+                       const svo_closest_out *out, void *stream);
+int svo_closest_voxels_host(svo_ctx *ctx, const svo_shape *queries, size_t n, const svo_closest_params *params,
+                            svo_closest *nearest, svo_contact *contacts);
+
 /* Information about the uploaded pool. */
 int svo_get_info(svo_ctx *ctx, size_t *n_nodes, int *max_depth, int *device);
 

@@ -43,7 +43,7 @@ EXPORTS = ("svo_create", "svo_set_buffer", "svo_set_buffer_v2", "svo_set_camera"
            "svo_set_lights", "svo_get_lights", "svo_light_rays", "svo_light_rays_host",
            "svo_set_objects", "svo_get_objects", "svo_object_rays", "svo_object_rays_host", "svo_trace_scene",
            "svo_trace_scene_host", "svo_scene_light_rays", "svo_scene_light_rays_host",
-           "svo_overlap_volumes", "svo_overlap_volumes_host")
+           "svo_overlap_volumes", "svo_overlap_volumes_host", "svo_closest_voxels", "svo_closest_voxels_host")
 # svo_ray: one caller-supplied ray of svo_trace_rays (world space, direction used as given)
 RAY_DTYPE = np.dtype([("origin", "<f4", (3,)), ("t_max", "<f4"), ("dir", "<f4", (3,)), ("reserved", "<u4")])
 assert RAY_DTYPE.itemsize == 32
@@ -71,6 +71,11 @@ assert SHAPE_DTYPE.itemsize == 32 and CONTACT_DTYPE.itemsize == 16 and OVERLAP_D
 SHAPE_BOX, SHAPE_SPHERE = 0, 1               # svo_shape.kind
 OVERLAP_ANY = 1                              # svo_overlap_params.flags: stop at the first result voxel
 OVERLAP_MAX_CONTACTS = 32
+# svo_closest: one query's answer of svo_closest_voxels (the queries are svo_shape spheres, the contacts svo_contact)
+CLOSEST_DTYPE = np.dtype([("point", "<f4", (3,)), ("d2", "<f4"), ("parent", "<u4"), ("meta", "<u4"), ("visits", "<u4"),
+                          ("flags", "<u4")])
+assert CLOSEST_DTYPE.itemsize == 32
+CLOSEST_UNBOUNDED = 1                        # svo_closest_params.flags: ignore the search radius
 SVO_OPT_SHADOW_RAYS = 1
 SVO_OPT_KERNEL_TIMING = 2
 SVO_OPT_COUNT_BEAM = 4
@@ -147,6 +152,22 @@ class SvoOverlapOut(ctypes.Structure):
 
 def overlap_params(root=0, max_contacts=0, any_hit=False, max_visits=0, coarse_level=0):
     return SvoOverlapParams(ctypes.sizeof(SvoOverlapParams), OVERLAP_ANY if any_hit else 0, int(root), int(max_contacts),
+                            int(max_visits), int(coarse_level))
+
+
+class SvoClosestParams(ctypes.Structure):
+    """svo_closest_params, versioned by its size."""
+    _fields_ = [("size", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("root", ctypes.c_uint32),
+                ("max_visits", ctypes.c_uint32), ("coarse_level", ctypes.c_uint32)]
+
+
+class SvoClosestOut(ctypes.Structure):
+    """svo_closest_out: device pointers (ints) of a closest-voxel query's outputs, each nullable."""
+    _fields_ = [("nearest", ctypes.c_void_p), ("contacts", ctypes.c_void_p), ("hitmask", ctypes.c_void_p)]
+
+
+def closest_params(root=0, unbounded=False, max_visits=0, coarse_level=0):
+    return SvoClosestParams(ctypes.sizeof(SvoClosestParams), CLOSEST_UNBOUNDED if unbounded else 0, int(root),
                             int(max_visits), int(coarse_level))
 
 
@@ -263,6 +284,8 @@ def lib():
         "svo_scene_light_rays_host": [vp, vp, sz, ctypes.c_uint32, vp, vp, vp, vp, i, vp, i, vp],
         "svo_overlap_volumes": [vp, vp, sz, ctypes.POINTER(SvoOverlapParams), ctypes.POINTER(SvoOverlapOut), vp],
         "svo_overlap_volumes_host": [vp, vp, sz, ctypes.POINTER(SvoOverlapParams), vp, vp],
+        "svo_closest_voxels": [vp, vp, sz, ctypes.POINTER(SvoClosestParams), ctypes.POINTER(SvoClosestOut), vp],
+        "svo_closest_voxels_host": [vp, vp, sz, ctypes.POINTER(SvoClosestParams), vp, vp],
         "svo_destroy": [vp],
         "svo_last_error": [],
         "svo_abi_version": [],

@@ -2568,6 +2568,50 @@ __global__ __launch_bounds__(TILE) void overlap_kernel(OverlapArgs a) {
     if (lane == 0 && a.hitmask) a.hitmask[blockIdx.x] = m;
 }
 
+// --------------------------------------------------------- closest voxels
+// svo_closest_voxels (svo_closest.h is the rule and holds the walk itself): overlap_kernel's shape -- one lane
+// per query, one wave64 per 64 consecutive queries, the walk's ancestor stack in the same two LDS arrays
+// ([level][lane], STACK_LEVELS levels, 12 bytes per lane and level), driven through OverlapFetch and
+// OverlapStack.  The best voxel so far lives in registers; the eight children's d2 are recomputed from
+// (level, i) when the walk returns to a descriptor, so the stack entry stays overlap's.  Lanes diverge: a wave
+// lasts as long as its longest search, which max_visits bounds.
+__global__ __launch_bounds__(TILE) void closest_kernel(ClosestArgs a) {
+    __shared__ uint2 s_nf[svo_volumes::STACK_LEVELS * TILE];
+    __shared__ uint32_t s_state[svo_volumes::STACK_LEVELS * TILE];
+    const int lane = (int)threadIdx.x;
+    const uint32_t i = blockIdx.x * TILE + (uint32_t)lane;
+    const bool in = i < a.n;
+    svo_volumes::Shape s = {};
+    if (in) {   // two 16-byte loads
+        const float4 *src = reinterpret_cast<const float4 *>(a.queries) + 2 * (size_t)i;
+        const float4 lo = src[0], hi = src[1];
+        s.p[0] = lo.x; s.p[1] = lo.y; s.p[2] = lo.z; s.kind = __float_as_uint(lo.w);
+        s.q[0] = hi.x; s.q[1] = hi.y; s.q[2] = hi.z;
+    }
+    bool found = false;
+    if (in) {
+        svo_nearest::Closest r = svo_nearest::nothing_found(0u, svo_nearest::FLAG_INVALID);
+        svo_volumes::Contact c = svo_volumes::unused_contact();
+        if (svo_nearest::query_valid(s)) {
+            OverlapFetch fetch{a.nodes, a.n_nodes};
+            OverlapStack stack{s_nf + lane, s_state + lane};
+            r = svo_nearest::walk(s, a.root, a.flags, a.max_visits, a.coarse_level, fetch, stack, c);
+        }
+        if (a.nearest) {   // two 16-byte stores
+            uint4 *dst = reinterpret_cast<uint4 *>(a.nearest) + 2 * (size_t)i;
+            dst[0] = make_uint4(__float_as_uint(r.point[0]), __float_as_uint(r.point[1]), __float_as_uint(r.point[2]),
+                                __float_as_uint(r.d2));
+            dst[1] = make_uint4(r.parent, r.meta, r.visits, r.flags);
+        }
+        if (a.contacts)
+            reinterpret_cast<uint4 *>(a.contacts)[i] = make_uint4(c.parent, c.meta, (uint32_t)c.key, (uint32_t)(c.key >> 32));
+        found = (r.flags & svo_nearest::FLAG_FOUND) != 0u;
+    }
+    // lane 0 is always inside the list (the grid is ceil(n / 64) waves); lanes past it vote 0
+    const lmask m = LM_OF(found);
+    if (lane == 0 && a.hitmask) a.hitmask[blockIdx.x] = m;
+}
+
 // ------------------------------------------------------------------ skybox
 // svo_set_skybox: the sky pass behind the primary launch.  One wave64 per 8x8 tile of the
 // launch's rows, in plain tile order (the pass has no heavy tiles to put first).  The tile's hit mask is
@@ -3893,6 +3937,13 @@ hipError_t launch_overlap(const OverlapArgs &a, hipStream_t stream) {
         return hipErrorInvalidValue;
     if (a.n == 0) return hipSuccess;
     hipLaunchKernelGGL(overlap_kernel, dim3((a.n + (uint32_t)TILE - 1u) / (uint32_t)TILE), dim3(TILE), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_closest(const ClosestArgs &a, hipStream_t stream) {
+    if (!a.nodes || !a.queries || a.max_visits == 0u || (!a.nearest && !a.contacts && !a.hitmask)) return hipErrorInvalidValue;
+    if (a.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(closest_kernel, dim3((a.n + (uint32_t)TILE - 1u) / (uint32_t)TILE), dim3(TILE), 0, stream, a);
     return hipGetLastError();
 }
 

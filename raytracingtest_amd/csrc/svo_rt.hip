@@ -2724,6 +2724,57 @@ int overlap_device(svo_ctx *c, const svo_shape *d_shapes, size_t n, const svo_ov
     return launched(svo::launch_overlap(a, s), "overlap launch");
 }
 
+// ---- closest voxels (svo_closest_voxels; svo_closest.h is the rule)
+// The caller's params as this library reads them, like read_overlap_params; max_visits comes out resolved.
+int read_closest_params(const svo_closest_params *params, svo_closest_params *k) {
+    std::memset(k, 0, sizeof *k);
+    if (params) {
+        if (params->size < 2 * sizeof(uint32_t)) return fail(SVO_ERR_ARG, "svo_closest_params.size must hold at least size and flags");
+        if (params->size > sizeof *k)
+            return fail(SVO_ERR_ARG, "svo_closest_params.size " + std::to_string(params->size) +
+                                         " is larger than this library's (" + std::to_string(sizeof *k) + "): a newer ABI");
+        std::memcpy(k, params, params->size);
+    }
+    k->size = sizeof *k;
+    if (k->flags & ~(uint32_t)SVO_CLOSEST_UNBOUNDED) return fail(SVO_ERR_ARG, "unknown closest flag bits");
+    if (k->max_visits > svo_nearest::MAX_VISITS) return fail(SVO_ERR_ARG, "max_visits must be 0 or lie in 1..2^24");
+    if (k->coarse_level > (uint32_t)svo_nearest::MAX_LEVEL) return fail(SVO_ERR_ARG, "coarse_level must be 0 or lie in 1..22");
+    if (k->max_visits == 0) k->max_visits = svo_nearest::DEFAULT_VISITS;
+    return SVO_OK;
+}
+
+// The checks the device and the host form share; out_error: the form's complaint about its outputs, or null.
+int check_closest_args(svo_ctx *ctx, const void *queries, size_t n, const svo_closest_params *params, const char *out_error,
+                       svo_closest_params *k) {
+    static_assert(sizeof(svo_closest) == sizeof(svo_nearest::Closest), "closest record layout");
+    if (!ctx) return fail(SVO_ERR_ARG, "null context");
+    if (!queries) return fail(SVO_ERR_ARG, "null query list");
+    if (out_error) return fail(SVO_ERR_ARG, out_error);
+    if (int rc = read_closest_params(params, k)) return rc;
+    if (int rc = check_batch_count(n, 1, "queries")) return rc;
+    if ((size_t)k->root >= batch_context(ctx)->capacity) return fail(SVO_ERR_ARG, "root outside the node-pool capacity");
+    return SVO_OK;
+}
+
+// One closest-voxel query on context c (single-device), its device selected: arguments and pool checked by the caller.
+int closest_device(svo_ctx *c, const svo_shape *d_queries, size_t n, const svo_closest_params &k, const svo_closest_out &out,
+                   hipStream_t s) {
+    svo::ClosestArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.nodes = c->d_nodes;
+    a.n_nodes = (uint32_t)std::min<size_t>(c->n_nodes, 0xFFFFFFFFu);
+    a.queries = reinterpret_cast<const svo_volumes::Shape *>(d_queries);
+    a.n = (uint32_t)n;
+    a.flags = k.flags;
+    a.root = k.root;
+    a.max_visits = k.max_visits;
+    a.coarse_level = k.coarse_level;
+    a.nearest = reinterpret_cast<svo_nearest::Closest *>(out.nearest);
+    a.contacts = reinterpret_cast<svo_volumes::Contact *>(out.contacts);
+    a.hitmask = reinterpret_cast<unsigned long long *>(out.hitmask);
+    return launched(svo::launch_closest(a, s), "closest launch");
+}
+
 }  // namespace
 
 extern "C" {
@@ -2937,6 +2988,42 @@ int svo_overlap_volumes_host(svo_ctx *ctx, const svo_shape *shapes, size_t n, co
         if (int rc = overlap_device(c, st.at<const svo_shape>(p_shapes), n, k, out, s)) return rc;
         if (int rc = st.download(summary, p_sum, 16 * n)) return rc;
         if (int rc = st.download(contacts, p_con, 16 * n_contacts)) return rc;
+        return st.finish();
+    });
+}
+
+int svo_closest_voxels(svo_ctx *ctx, const svo_shape *d_queries, size_t n, const svo_closest_params *params,
+                       const svo_closest_out *out, void *stream) {
+    const char *out_error = !out ? "null svo_closest_out"
+                            : !out->nearest && !out->contacts && !out->hitmask ? "every closest output is null"
+                                                                               : nullptr;
+    svo_closest_params k;
+    if (int rc = check_closest_args(ctx, d_queries, n, params, out_error, &k)) return rc;
+    if (((uintptr_t)d_queries | (uintptr_t)out->nearest | (uintptr_t)out->contacts) & 15u)
+        return fail(SVO_ERR_ARG, "queries, nearest records and contacts must be 16-byte aligned");
+    if ((uintptr_t)out->hitmask & 7u) return fail(SVO_ERR_ARG, "the hit mask must be 8-byte aligned");
+    if (n == 0) return SVO_OK;
+    return on_device(ctx, "svo_closest_voxels", stream, true,
+                     [&](svo_ctx *c, hipStream_t s) { return closest_device(c, d_queries, n, k, *out, s); });
+}
+
+int svo_closest_voxels_host(svo_ctx *ctx, const svo_shape *queries, size_t n, const svo_closest_params *params,
+                            svo_closest *nearest, svo_contact *contacts) {
+    const char *out_error = !nearest && !contacts ? "every closest output is null" : nullptr;
+    svo_closest_params k;
+    if (int rc = check_closest_args(ctx, queries, n, params, out_error, &k)) return rc;
+    if (n == 0) return SVO_OK;
+    return on_device(ctx, "svo_closest_voxels_host", nullptr, true, [&](svo_ctx *c, hipStream_t s) {
+        HostStage st(c);
+        const size_t p_queries = st.part(32 * n), p_near = st.part(nearest ? 32 * n : 0), p_con = st.part(contacts ? 16 * n : 0);
+        if (int rc = st.begin()) return rc;
+        if (int rc = st.upload(p_queries, queries, 32 * n)) return rc;
+        svo_closest_out out{};
+        out.nearest = st.at_if<svo_closest>(nearest, p_near);
+        out.contacts = st.at_if<svo_contact>(contacts, p_con);
+        if (int rc = closest_device(c, st.at<const svo_shape>(p_queries), n, k, out, s)) return rc;
+        if (int rc = st.download(nearest, p_near, 32 * n)) return rc;
+        if (int rc = st.download(contacts, p_con, contacts ? 16 * n : 0)) return rc;
         return st.finish();
     });
 }

@@ -15,6 +15,7 @@
 
 #include "svo_light.h"
 #include "svo_object.h"
+#include "svo_closest.h"
 #include "svo_overlap.h"
 #include "svo_sky.h"
 
@@ -423,5 +424,24 @@ struct OverlapArgs {
     unsigned long long *hitmask;
 };
 hipError_t launch_overlap(const OverlapArgs &a, hipStream_t stream);
+
+// Closest voxels (svo_closest_voxels; svo_kernel.hip closest_kernel, svo_closest.h is the rule and the walk):
+// one lane per query, one wave64 per 64 consecutive queries.  Every non-null output is fully written for all
+// n: nearest n records, contacts n entries (nothing found: {0xFFFFFFFF, 0, all ones}), hitmask ceil(n / 64)
+// words with the tail bits 0.  Reads the node pool only.
+struct ClosestArgs {
+    const uint2 *nodes;
+    uint32_t n_nodes;                     // fetches at or past it read the zero descriptor
+    const svo_volumes::Shape *queries;    // 16-byte aligned
+    uint32_t n;                           // queries (<= 2^31 - 1)
+    uint32_t flags;                       // svo_nearest::UNBOUNDED
+    uint32_t root;
+    uint32_t max_visits;                  // resolved: 1 .. 2^24
+    uint32_t coarse_level;                // 0: none
+    svo_nearest::Closest *nearest;        // 16-byte aligned, like contacts
+    svo_volumes::Contact *contacts;
+    unsigned long long *hitmask;
+};
+hipError_t launch_closest(const ClosestArgs &a, hipStream_t stream);
 
 }  // namespace svo

@@ -23,6 +23,8 @@ Beyond the reference (one GPU, one Dispatch):
   trace_rays_device(...)         SVO.Trace(Ray), Interfaces.cs:6-15) on the GPU
   OverlapVolumes(shapes)         which voxels boxes and spheres touch (no reference counterpart)
   overlap_volumes_device(...)
+  ClosestVoxels(queries)         the nearest voxel to a point, its squared distance and the closest point
+  closest_voxels_device(...)     on it (no reference counterpart)
 Errors surface as SvoError (the C-ABI status + svo_last_error text) instead of
 Unity's silent shader failures.  There is no CPU fallback.
 """
@@ -737,6 +739,36 @@ class RaytracingMaster:
         out = _lib.SvoOverlapOut(summary, contacts, hitmask)
         check(_lib.lib().svo_overlap_volumes(self._ctx, shapes_ptr, int(n), ctypes.byref(prm), ctypes.byref(out), stream),
               "svo_overlap_volumes")
+
+    # --------------------------------------------------------- closest voxels
+    def ClosestVoxels(self, queries, root=0, unbounded=False, max_visits=0, coarse_level=0, contacts=False):
+        """How far is each point from the surface, and where is the closest point on it (svo_closest_voxels_host;
+        closest.closest_model is its Python statement)?  queries: svo_shape spheres (closest.make_queries: the
+        point and a search radius), world space, or the frame of the tree at `root` (0: the terrain; a placed
+        object: closest.object_queries).  unbounded: ignore the radius; max_visits: the walk's budget of
+        descriptor fetches (0: 65536) -- a walk it ends returns the best so far; coarse_level: the voxels of
+        that level count instead of what lies below.  Blocking.  Returns the answers (CLOSEST_DTYPE [n]: point,
+        d2 -- squared, the caller takes the root --, parent, meta, visits, flags: bit 0 found, 1 budget,
+        2 overflow, 0x10 invalid query), or (answers, contacts [n] CONTACT_DTYPE) with contacts=True."""
+        queries = np.ascontiguousarray(queries, _lib.SHAPE_DTYPE).reshape(-1)
+        n = len(queries)
+        prm = _lib.closest_params(root, unbounded, max_visits, coarse_level)
+        nearest = np.zeros(n, _lib.CLOSEST_DTYPE)
+        found = np.zeros(n, _lib.CONTACT_DTYPE) if contacts else None
+        check(_lib.lib().svo_closest_voxels_host(self._ctx, queries.ctypes.data, n, ctypes.byref(prm), nearest.ctypes.data,
+                                                 None if found is None else found.ctypes.data),
+              "svo_closest_voxels_host")
+        return nearest if found is None else (nearest, found)
+
+    def closest_voxels_device(self, queries_ptr, n, nearest=None, contacts=None, hitmask=None, root=0, unbounded=False,
+                              max_visits=0, coarse_level=0, stream=None):
+        """Asynchronous svo_closest_voxels on device buffers: queries_ptr = n svo_shape records (32 bytes each,
+        16-byte aligned); nearest (n x 32 bytes), contacts (n x 16 bytes) and hitmask (ceil(n / 64) uint64) are
+        raw device pointers, each nullable, and are fully written."""
+        prm = _lib.closest_params(root, unbounded, max_visits, coarse_level)
+        out = _lib.SvoClosestOut(nearest, contacts, hitmask)
+        check(_lib.lib().svo_closest_voxels(self._ctx, queries_ptr, int(n), ctypes.byref(prm), ctypes.byref(out), stream),
+              "svo_closest_voxels")
 
     def beam_starts_device(self, width, height, starts_ptr, band=None, stream=None):
         """svo_beam_starts: every primary ray's beam start (SVO-space t, -inf: the cube entry) into a

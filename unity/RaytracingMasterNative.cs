@@ -207,6 +207,27 @@ public static class SvoNative {
     [DllImport(Lib)] public static extern int svo_overlap_volumes_host(IntPtr ctx, [In] SvoShape[] shapes, UIntPtr n,
                                                                        ref SvoOverlapParams prm, [Out] SvoOverlap[] summary,
                                                                        [Out] SvoContact[] contacts);
+    // Closest voxels (svo_rt.h): the nearest voxel to a point, its squared distance and the closest point on it.
+    // A query is an SvoShape of kind ShapeSphere: the point and a search radius (ClosestUnbounded ignores it).
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoClosest {                    // == svo_closest, 32 bytes
+        public float pointX, pointY, pointZ;      // closest point on the voxel's closed box; not found: 0, 0, 0
+        public float d2;                          // squared distance; not found: +inf
+        public uint parent, meta, visits, flags;  // flags: bit0 found, bit1 budget, bit2 overflow, 0x10 invalid query
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoClosestParams {              // == svo_closest_params, versioned by size
+        public uint size, flags, root, maxVisits, coarseLevel;
+    }
+    [StructLayout(LayoutKind.Sequential)]
+    public struct SvoClosestOut { public IntPtr nearest, contacts, hitmask; }   // device pointers
+    public const uint ClosestUnbounded = 1;
+    [DllImport(Lib)] public static extern int svo_closest_voxels(IntPtr ctx, IntPtr dQueries, UIntPtr n,
+                                                                 ref SvoClosestParams prm, ref SvoClosestOut output,
+                                                                 IntPtr stream);
+    [DllImport(Lib)] public static extern int svo_closest_voxels_host(IntPtr ctx, [In] SvoShape[] queries, UIntPtr n,
+                                                                      ref SvoClosestParams prm, [Out] SvoClosest[] nearest,
+                                                                      [Out] SvoContact[] contacts);
 
     [StructLayout(LayoutKind.Sequential)]
     public struct SvobResult {   // == svob_result
@@ -390,6 +411,28 @@ public class RaytracingMasterNative : MonoBehaviour {
         int n = 0;
         for (int i = 0; i < summary.Length; i++)
             if ((summary[i].flags & 1) != 0) n++;
+        return n;
+    }
+
+    // How far is each point from the surface, and where is the closest point on it (svo_closest_voxels_host)?
+    // Depenetration, conservative advancement (step by distance - r), snap-to-surface, clearance tests.  Queries
+    // in world space (SvoNative.SvoShape of kind ShapeSphere: the point, qX the search radius); root 0 is the
+    // terrain.  unbounded: ignore the radius; maxVisits: the walk's budget of descriptor fetches (0: 65536) -- a
+    // walk it ends answers with the best so far.  d2 is squared: take Mathf.Sqrt.  Returns how many found a voxel.
+    public int ClosestVoxels(SvoNative.SvoShape[] queries, out SvoNative.SvoClosest[] nearest,
+                             out SvoNative.SvoContact[] contacts, uint root = 0, bool unbounded = false,
+                             uint maxVisits = 0, uint coarseLevel = 0) {
+        nearest = new SvoNative.SvoClosest[queries.Length];
+        contacts = new SvoNative.SvoContact[queries.Length];
+        if (queries.Length == 0) return 0;
+        var prm = new SvoNative.SvoClosestParams {
+            size = (uint)Marshal.SizeOf(typeof(SvoNative.SvoClosestParams)),
+            flags = unbounded ? SvoNative.ClosestUnbounded : 0u, root = root, maxVisits = maxVisits, coarseLevel = coarseLevel };
+        SvoNative.Check(SvoNative.svo_closest_voxels_host(_ctx, queries, (UIntPtr)queries.Length, ref prm, nearest, contacts),
+                        "svo_closest_voxels_host");
+        int n = 0;
+        for (int i = 0; i < nearest.Length; i++)
+            if ((nearest[i].flags & 1) != 0) n++;
         return n;
     }
 
