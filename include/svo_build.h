@@ -80,6 +80,8 @@ typedef struct svob_limits {
                                  a slab with more surface leaves regrows it to 1.25 x count + 1024 */
     int32_t  slab_rows;       /* leaf planes per slab, overrides cell_bytes (0: the rule above); < 0: error */
     int32_t  max_blocks;      /* cap on the blocks (of 256 threads) of each launch (0: 65,536); < 0: error */
+    uint64_t launch_candidates;   /* meshes: candidate voxels per launch of the overlap kernel (0: 2^28); any
+                                     value >= 1 is taken, a slab with more candidates takes several launches */
 } svob_limits;
 
 /* What the leaf pass did; filled by the _ex entries when non-NULL.  `size` is set by the
@@ -92,6 +94,9 @@ typedef struct svob_report {
     uint32_t normals_regrown;   /* 1: the list was re-allocated for the normal pass (all leaves > capacity) */
     uint32_t reserved;          /* 0 */
     uint64_t list_capacity;     /* capacity of the surface list when the last slab was classified */
+    uint32_t overlap_launches;  /* meshes: launches of the overlap kernel, the sum over the slabs that hold a
+                                   candidate of ceil(slab's candidates / launch_candidates); samplers: 0 */
+    uint32_t reserved2;         /* 0 */
 } svob_report;
 
 /* Leaf planes per slab for max_level under `limits` (NULL: defaults).  Pure host
@@ -143,6 +148,9 @@ int svob_surface_leaves_ex(int device, int sampler, int max_level, const svob_li
  * One slab up to max_level 10, 128 planes at max_level 11, 2 at max_level 14.  list_capacity,
  * max_blocks and svob_report keep their meaning: `relaunches` counts compactions repeated because
  * a slab held more leaves than the list, `normals_regrown` the re-allocation for the attribute pass.
+ * Work is spread per candidate voxel (the voxels of every triangle's clipped box): one launch of the
+ * overlap kernel takes at most `launch_candidates` of a slab's candidates (2^28), the next one goes
+ * on where it ended, in the middle of a triangle's box or not; `overlap_launches` counts them.
  */
 enum { SVOB_MESH_FLIP_WINDING = 1 };
 typedef struct svob_mesh {          /* versioned by size like svob_limits */

@@ -28,6 +28,8 @@
 //                  (classify_kernel stores only while k < cap); the normal pass
 //                  re-allocates when all leaves exceed the capacity.
 //   max_blocks     cap on each launch's blocks, 65,536; the kernels' stride loops cover the rest.
+//   launch_candidates  meshes only: candidates of one mesh_overlap_kernel launch, 2^28; a slab with more takes
+//                  ceil(total / launch_candidates) launches (svob_report.overlap_launches sums them).
 // None of them changes a result.  svob_report says which of these paths a call took.
 // The mesh pass (svob_build_mesh, "meshes" below) reads the same fields for its owner grid of 4-byte
 // cells without a halo: rows = clamp(cell_bytes / (4 n^2), 1, n), and a budget below one plane is refused.
@@ -627,6 +629,7 @@ struct Limits {
     uint64_t list_capacity = 0;   // 0: max(1 Mi, 4 n^2)
     int32_t slab_rows = 0;        // 0: from cell_bytes
     int32_t max_blocks = 65536;
+    uint64_t launch_candidates = 1ull << 28;   // meshes: candidates per mesh_overlap_kernel launch
 };
 
 int read_limits(const svob_limits *in, Limits *out) {
@@ -646,6 +649,7 @@ int read_limits(const svob_limits *in, Limits *out) {
     out->list_capacity = k.list_capacity;
     out->slab_rows = k.slab_rows;
     if (k.max_blocks) out->max_blocks = k.max_blocks;
+    if (k.launch_candidates) out->launch_candidates = k.launch_candidates;
     return SVOB_OK;
 }
 
@@ -779,11 +783,11 @@ int surface_leaves_gpu(int device, int type, int max_level, const Limits &lim, s
 //     mesh_overlap_kernel  one lane per CANDIDATE VOXEL: candidate g belongs to the triangle t with
 //                          scan[t] <= g < scan[t + 1], found by a search over the whole scan for the wave's first
 //                          and last candidate (wave-uniform) and refined per lane between the two; the rule, and
-//                          atomicMin(cell, t) on a hit.  At most MESH_LAUNCH_CANDIDATES per launch.
+//                          atomicMin(cell, t) on a hit.  At most svob_limits.launch_candidates (2^28) per launch;
+//                          svob_report.overlap_launches counts the launches.
 //     mesh_compact_kernel  occupied cells -> (morton, owner) through classify_kernel's counter / capacity protocol
 //   host: sort by code (codes are unique); mesh_attr_kernel: normal and colour of every sorted leaf from its owner.
 using svo_voxelize::Tri;
-constexpr uint64_t MESH_LAUNCH_CANDIDATES = 1ull << 28;
 
 struct Mesh {   // svob_mesh after read_mesh
     uint32_t flags = 0;
@@ -903,22 +907,10 @@ __global__ void __launch_bounds__(256) mesh_overlap_kernel(const Tri *__restrict
             const Tri &t = tris[ti];
             const uint64_t local = g - scan[ti];
             const uint32_t bx = (uint32_t)(t.bhi[0] - t.blo[0] + 1), by = (uint32_t)(t.bhi[1] - t.blo[1] + 1);
-            const uint64_t plane = (uint64_t)bx * by;
-            uint32_t ix, iy, iz;
-            if (((local | plane) >> 32) == 0) {
-                const uint32_t l = (uint32_t)local, p = (uint32_t)plane;
-                iz = l / p;
-                const uint32_t r = l - iz * p;
-                iy = r / bx;
-                ix = r - iy * bx;
-            } else {
-                iz = (uint32_t)(local / plane);
-                const uint64_t r = local - (uint64_t)iz * plane;
-                iy = (uint32_t)(r / bx);
-                ix = (uint32_t)(r - (uint64_t)iy * bx);
-            }
+            uint32_t at[3];
+            svo_voxelize::candidate_voxel(local, bx, by, at);
             const int zl = t.blo[2] > z0 ? t.blo[2] : z0;
-            const int i[3] = { t.blo[0] + (int)ix, t.blo[1] + (int)iy, zl + (int)iz };
+            const int i[3] = { t.blo[0] + (int)at[0], t.blo[1] + (int)at[1], zl + (int)at[2] };
             // inside the box and the slab by construction; the compare keeps a store inside the grid whatever the scan holds
             hit = i[0] <= t.bhi[0] && i[1] <= t.bhi[1] && i[2] <= t.bhi[2] && i[2] <= z1 && svo_voxelize::overlaps(t, i);
             if (hit) atomicMin(&grid[((size_t)(i[2] - z0) * n + (size_t)i[1]) * n + (size_t)i[0]], ti);
@@ -1164,8 +1156,10 @@ int mesh_leaves_gpu(int device, const Mesh &mesh, int max_level, int rows, const
         if (e != hipSuccess) { cleanup(); return fail(SVOB_ERR_HIP, std::string("mesh count: ") + hipGetErrorString(e)); }
         if (total == 0) continue;   // no triangle's box reaches this slab
         e = hipMemset(grid, 0xFF, plane * (size_t)zc * sizeof(uint32_t));
-        for (uint64_t c0 = 0; e == hipSuccess && c0 < total; c0 += MESH_LAUNCH_CANDIDATES) {
-            const uint64_t c1 = std::min<uint64_t>(total, c0 + MESH_LAUNCH_CANDIDATES);   // 64-bit: a slab may hold more
+        for (uint64_t c0 = 0, c1 = 0; e == hipSuccess && c0 < total; c0 = c1) {
+            // 64-bit: a slab may hold more than one launch takes; the limit may be anything from 1 to 2^64 - 1
+            c1 = total - c0 > lim.launch_candidates ? c0 + lim.launch_candidates : total;
+            ++r.overlap_launches;
             clock.begin(MESH_K_OVERLAP);
             hipLaunchKernelGGL(mesh_overlap_kernel, dim3(blocks_for((size_t)(c1 - c0), lim)), dim3(256), 0, 0, dtris, dscan,
                                n_tri, n, z0, z1, c0, c1, grid, dstats + 3);

@@ -160,6 +160,35 @@ SVO_VOX_FN uint64_t candidates(const Tri &t, int z0, int z1) {
     return (uint64_t)(t.bhi[0] - t.blo[0] + 1) * (uint64_t)(t.bhi[1] - t.blo[1] + 1) * (uint64_t)(zh - zl + 1);
 }
 
+// Candidate `local` of a box that is bx wide and by deep, counted x first, then y, then z:
+//   out = (local mod bx, (local div bx) mod by, local div (bx by)),  the last one modulo 2^32.
+// Two forms of the same integers: 32-bit divisions while local and the plane bx by both fit 32 bits (every
+// triangle's box up to a 1024^3 grid, and most beyond), 64-bit ones otherwise.  The builder's overlap kernel
+// adds the box's (and the slab's) lower corner; a candidate of the box has out[2] below the box's height.
+SVO_VOX_FN void candidate_voxel_32(uint32_t local, uint32_t bx, uint32_t plane, uint32_t out[3]) {
+    const uint32_t iz = local / plane;
+    const uint32_t r = local - iz * plane;
+    const uint32_t iy = r / bx;
+    out[0] = r - iy * bx;
+    out[1] = iy;
+    out[2] = iz;
+}
+
+SVO_VOX_FN void candidate_voxel_64(uint64_t local, uint32_t bx, uint64_t plane, uint32_t out[3]) {
+    const uint64_t iz = local / plane;
+    const uint64_t r = local - iz * plane;
+    const uint64_t iy = r / bx;
+    out[0] = (uint32_t)(r - iy * bx);
+    out[1] = (uint32_t)iy;
+    out[2] = (uint32_t)iz;
+}
+
+SVO_VOX_FN void candidate_voxel(uint64_t local, uint32_t bx, uint32_t by, uint32_t out[3]) {
+    const uint64_t plane = (uint64_t)bx * by;
+    if (((local | plane) >> 32) == 0) candidate_voxel_32((uint32_t)local, bx, (uint32_t)plane, out);
+    else candidate_voxel_64(local, bx, plane, out);
+}
+
 // Steps 2 and 3 for voxel i (inside the box) of a triangle that is not skipped.
 SVO_VOX_FN bool overlaps(const Tri &t, const int i[3]) {
     float lo[3], hi[3];

@@ -22,13 +22,15 @@ class _Result(ctypes.Structure):
 class _Limits(ctypes.Structure):
     """svob_limits (include/svo_build.h): zero is the default of every field."""
     _fields_ = [("size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("cell_bytes", ctypes.c_uint64),
-                ("list_capacity", ctypes.c_uint64), ("slab_rows", ctypes.c_int32), ("max_blocks", ctypes.c_int32)]
+                ("list_capacity", ctypes.c_uint64), ("slab_rows", ctypes.c_int32), ("max_blocks", ctypes.c_int32),
+                ("launch_candidates", ctypes.c_uint64)]
 
 
 class _Report(ctypes.Structure):
     _fields_ = [("size", ctypes.c_uint32), ("slabs", ctypes.c_uint32), ("slab_rows", ctypes.c_uint32),
                 ("relaunches", ctypes.c_uint32), ("normals_regrown", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
-                ("list_capacity", ctypes.c_uint64)]
+                ("list_capacity", ctypes.c_uint64), ("overlap_launches", ctypes.c_uint32),
+                ("reserved2", ctypes.c_uint32)]
 
 
 class _Mesh(ctypes.Structure):
@@ -45,8 +47,9 @@ class _MeshStats(ctypes.Structure):
 
 MESH_FLIP_WINDING = 1
 MESH_STATS_FIELDS = ("degenerate", "outside", "candidates", "overlaps")
-LIMIT_FIELDS = ("cell_bytes", "slab_rows", "list_capacity", "max_blocks")
+LIMIT_FIELDS = ("cell_bytes", "slab_rows", "list_capacity", "max_blocks", "launch_candidates")
 REPORT_FIELDS = ("slabs", "slab_rows", "relaunches", "normals_regrown", "list_capacity")
+MESH_REPORT_FIELDS = REPORT_FIELDS + ("overlap_launches",)   # the mesh entries' report; the samplers leave it 0
 
 
 def _limits(limits):
@@ -66,8 +69,8 @@ def _new_report():
     return _Report(size=ctypes.sizeof(_Report))
 
 
-def _report_dict(rep):
-    return {k: int(getattr(rep, k)) for k in REPORT_FIELDS}
+def _report_dict(rep, fields=REPORT_FIELDS):
+    return {k: int(getattr(rep, k)) for k in fields}
 
 
 _blib = None
@@ -208,7 +211,8 @@ def build_mesh_svo(positions, triangles, max_level, colors=None, flip=False, dev
     """svob_build_mesh: an indexed triangle mesh (positions [v, 3] in the cube's unit frame [0,1]^3, triangles
     [t, 3], optional per-vertex rgb) voxelised on the GPU by the rule of voxelize.py and laid out as
     build_from_leaves does.  flip: SVOB_MESH_FLIP_WINDING.  limits: as build_sampler_svo (they never change the
-    result).  report=True: returns (svo, dict of REPORT_FIELDS, dict of MESH_STATS_FIELDS)."""
+    result; "launch_candidates" cuts a slab's candidates into launches of the overlap kernel).  report=True:
+    returns (svo, dict of MESH_REPORT_FIELDS, dict of MESH_STATS_FIELDS)."""
     m, keep = _mesh(positions, triangles, colors, flip)
     res = _Result()
     rep = _new_report()
@@ -219,7 +223,7 @@ def build_mesh_svo(positions, triangles, max_level, colors=None, flip=False, dev
     try:
         data = _to_svodata(res, prefer_v1)
         data.n_leaves = int(res.n_leaves)
-        return (data, _report_dict(rep), _stats_dict(st)) if report else data
+        return (data, _report_dict(rep, MESH_REPORT_FIELDS), _stats_dict(st)) if report else data
     finally:
         blib().svob_free(ctypes.byref(res))
 
@@ -238,7 +242,7 @@ def mesh_profile(enable):
 def mesh_leaves(positions, triangles, max_level, colors=None, flip=False, device=0, limits=None, report=False):
     """svob_mesh_leaves: (Morton codes uint64[m] sorted, normals float32[m, 3], colours float32[m, 3] or None,
     owner uint32[m]) -- voxelize.voxelize's result at depth max_level - 1, from the GPU; with report=True two more
-    items, the dicts of REPORT_FIELDS and MESH_STATS_FIELDS."""
+    items, the dicts of MESH_REPORT_FIELDS and MESH_STATS_FIELDS."""
     m, keep = _mesh(positions, triangles, colors, flip)
     n = ctypes.c_size_t()
     ptrs = [ctypes.c_void_p() for _ in range(4)]   # morton, normals, colours, owner
@@ -260,7 +264,7 @@ def mesh_leaves(positions, triangles, max_level, colors=None, flip=False, device
         col = arr(ptrs[2], ctypes.c_float, (k, 3), np.float32) if ptrs[2].value else None
         owner = arr(ptrs[3], ctypes.c_uint32, (k,), np.uint32)
         out = (codes, nrm, col, owner)
-        return out + (_report_dict(rep), _stats_dict(st)) if report else out
+        return out + (_report_dict(rep, MESH_REPORT_FIELDS), _stats_dict(st)) if report else out
     finally:
         for p in ptrs:
             blib().svob_free_ptr(p)

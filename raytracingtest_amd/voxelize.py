@@ -70,11 +70,21 @@ class Tri:
 
     def overlaps(self):
         """Steps 2 and 3 for every voxel of the box: a bool array [z, y, x] over the box."""
-        v, N = self.v, self.n
         ax = [np.arange(self.blo[c], self.bhi[c] + 1, dtype=np.int64) for c in range(3)]
         shape = [(1, 1, -1), (1, -1, 1), (-1, 1, 1)]
         lo = [ax[c].astype(F).reshape(shape[c]) for c in range(3)]
         hi = [(ax[c] + 1).astype(F).reshape(shape[c]) for c in range(3)]
+        return np.broadcast_to(self._rule(lo, hi), (len(ax[2]), len(ax[1]), len(ax[0])))
+
+    def overlaps_at(self, ijk):
+        """Steps 2 and 3 for the listed voxels ijk [m, 3] (integers inside the box): bool [m].  The header allows
+        any pruning of candidates; this is `overlaps` on a caller's selection of them."""
+        ijk = np.asarray(ijk, np.int64).reshape(-1, 3)
+        return self._rule([ijk[:, c].astype(F) for c in range(3)], [(ijk[:, c] + 1).astype(F) for c in range(3)])
+
+    def _rule(self, lo, hi):
+        """lo, hi: per axis the voxels' lower and upper faces as float32 arrays that broadcast together."""
+        v, N = self.v, self.n
         with np.errstate(all="ignore"):
             d = [(hi[c] if N[c] > 0 else lo[c]) - v[0, c] for c in range(3)]
             s = (N[0] * d[0] + N[1] * d[1]) + N[2] * d[2]
@@ -82,7 +92,7 @@ class Tri:
             for u, w, e, au, av, elo, hiw in self.edges:
                 p = au * ((hi[u] if au > 0 else lo[u]) - v[e, u]) + av * ((hi[w] if av > 0 else lo[w]) - v[e, w])
                 ok = ok & (p >= elo) & (p <= hiw)
-        return np.broadcast_to(ok, (len(ax[2]), len(ax[1]), len(ax[0])))
+        return ok
 
     def normal(self, flip=False):
         return (-self.unit if flip else self.unit).astype(F)

@@ -86,8 +86,22 @@ def test_limits_struct_is_versioned_by_size():
     import ctypes
     L = nb.blib()
     lim = nb._Limits(size=ctypes.sizeof(nb._Limits), slab_rows=3)
-    assert ctypes.sizeof(nb._Limits) == 32 and ctypes.sizeof(nb._Report) == 32
+    # launch_candidates (svob_limits) and overlap_launches (svob_report) were appended: the older fields keep their
+    # offsets, and a caller compiled against the 32-byte structs is read and written up to its 32 bytes
+    assert ctypes.sizeof(nb._Limits) == 40 and ctypes.sizeof(nb._Report) == 40
+    assert [getattr(nb._Limits, k).offset for k in ("size", "reserved", "cell_bytes", "list_capacity", "slab_rows",
+                                                    "max_blocks", "launch_candidates")] == [0, 4, 8, 16, 24, 28, 32]
+    assert [getattr(nb._Report, k).offset for k in ("size", "slabs", "slab_rows", "relaunches", "normals_regrown",
+                                                    "reserved", "list_capacity", "overlap_launches")] == \
+        [0, 4, 8, 12, 16, 20, 24, 32]
     assert L.svob_slab_rows(ML, ctypes.byref(lim)) == 3
+    lim.size = nb._Limits.launch_candidates.offset   # a caller compiled before launch_candidates existed
+    lim.launch_candidates = 2 ** 64 - 1              # past its size: not read
+    assert L.svob_slab_rows(ML, ctypes.byref(lim)) == 3
+    lim.size = ctypes.sizeof(nb._Limits)
+    for value in (0, 1, 2 ** 28, 2 ** 64 - 1):       # every value is accepted; 0 is the default
+        lim.launch_candidates = value
+        assert L.svob_slab_rows(ML, ctypes.byref(lim)) == 3
     lim.size = nb._Limits.slab_rows.offset   # a caller compiled before slab_rows existed
     assert L.svob_slab_rows(ML, ctypes.byref(lim)) == N
     lim.size = 8

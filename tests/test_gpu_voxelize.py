@@ -3,7 +3,11 @@
 References: voxelize.voxelize (numpy, the rule's statement; tests/test_voxelize.py pins it to the header and to a
 float64 model) for leaves, owners, normals, colours and the statistics; native_builder.build_from_leaves (the host
 layout) of those leaves for the pool; the CPU oracle and tests/object_util.py's model for the pipeline
-mesh -> pool -> object."""
+mesh -> pool -> object.  At 512^3 (span9, ico6_9) the reference is voxelize_util.band_reference, which
+tests/test_voxelize.py pins to voxelize.voxelize and to the header; the launch-chunk tests compare with the default
+run and with the host's count of launches."""
+import ctypes
+import functools
 import os
 import subprocess
 
@@ -85,7 +89,7 @@ def test_limits_never_change_a_result(gpu, limits):
     col = vu.vertex_colors(pos)
     base = leaves("ico2")
     assert base[4] == {"slabs": 1, "slab_rows": n, "relaunches": 0, "normals_regrown": 0,
-                       "list_capacity": max(1 << 20, 4 * n * n)}
+                       "list_capacity": max(1 << 20, 4 * n * n), "overlap_launches": 1}
     same_leaves(base, vu.reference("ico2"), "default")
     got = leaves("ico2", limits=limits)
     for a, b in zip(got[:4], base[:4]):
@@ -181,6 +185,174 @@ def test_render_of_the_mesh_pool_equals_the_oracle(gpu, oracle_mod, ico_pool):
     ocam = oracle_mod.make_camera(c2w, inv_proj, (0.5, 0.5), main_light())
     ref_hits, ref_rgba, _ = oracle_mod.render(qu.oracle_svo(oracle_mod, ico_pool), ocam, w, h)
     assert np.count_nonzero(ref_hits["flags"] & 1) > 100   # the oracle sees the sphere in 177 pixels
+    assert hits.reshape(-1).tobytes() == ref_hits.tobytes()
+    np.testing.assert_allclose(rgba.reshape(-1, 4), ref_rgba, rtol=1e-5, atol=1e-6)
+
+
+# ------------------------------------------------------------------ 12. launch chunks: the edges of mesh_overlap_kernel's launches
+def slab_totals(name, rows):
+    """Candidates of every z-slab of `rows` planes, on the host from the triangles' boxes."""
+    n = 1 << vu.mesh(name)[2]
+    b = vu.batch_of(name)
+    return [int(b.candidates(z0, min(z0 + rows, n) - 1).sum()) for z0 in range(0, n, rows)]
+
+
+def launches(totals, launch):
+    return sum(-(-t // launch) for t in totals if t)
+
+
+@functools.lru_cache(maxsize=None)
+def default_leaves(name):
+    """The default-limits run of a 64^3 mesh, checked once against numpy: what every chunked run must reproduce."""
+    got = leaves(name)
+    same_leaves(got, vu.reference(name), name)
+    assert got[5] == vu.reference(name)[4] and got[4]["slabs"] == 1 and got[4]["overlap_launches"] == 1
+    return got
+
+
+def check_chunked(name, limits, rows):
+    """One run under `limits`: bytes and statistics of the default run, and the launches the host arithmetic gives."""
+    base = default_leaves(name)
+    got = leaves(name, limits=limits)
+    for a, b in zip(got[:4], base[:4]):
+        assert a.tobytes() == b.tobytes(), (name, limits)
+    assert got[5] == base[5], (name, limits)
+    totals = slab_totals(name, rows)
+    assert got[4]["slabs"] == len(totals) and got[4]["overlap_launches"] == launches(totals, limits["launch_candidates"]), \
+        (name, limits, got[4])
+    return got[4]["overlap_launches"]
+
+
+@pytest.mark.parametrize("extra", [{}, {"slab_rows": 3}, {"max_blocks": 1}], ids=["alone", "slab_rows3", "max_blocks1"])
+@pytest.mark.parametrize("name", ["bigtiny", "ico2"])
+def test_launch_chunks_never_change_a_result(gpu, name, extra):
+    """svob_limits.launch_candidates cuts a slab's candidates into launches that start at c_begin > 0 and end
+    inside a wave (63, 65, 1000), on a wave's edge (64, 256), inside a triangle's box (bigtiny's spanning triangle
+    holds 97 % of the candidates) and one candidate before, at and after the slab's end T."""
+    n = 1 << vu.mesh(name)[2]
+    rows = extra.get("slab_rows", n)
+    totals = slab_totals(name, rows)
+    top = max(totals)
+    assert sum(totals) == vu.reference(name)[4]["candidates"] and top > 4097 + 64
+    if not extra:
+        assert default_leaves(name)[4]["overlap_launches"] == 1   # the default limit: one launch at 64^3
+    seen = {}
+    for launch in (1000, 256, 65, 64, 63, 4097, top - 1, top, top + 1):
+        seen[launch] = check_chunked(name, dict(extra, launch_candidates=launch), rows)
+    slabs = sum(1 for t in totals if t)
+    assert seen[63] > seen[64] > seen[65] > seen[4097] > seen[top - 1] == slabs + totals.count(top)
+    assert seen[top] == seen[top + 1] == slabs
+
+
+@pytest.mark.parametrize("extra", [{}, {"slab_rows": 3}, {"max_blocks": 1}], ids=["alone", "slab_rows3", "max_blocks1"])
+def test_one_candidate_per_launch(gpu, extra):
+    """launch_candidates 1 on the edge cases (skipped triangles, boxes clipped at the grid's faces): every
+    candidate is a launch of its own."""
+    n = 16
+    count = check_chunked("all_edges", dict(extra, launch_candidates=1), extra.get("slab_rows", n))
+    assert count == vu.reference("all_edges")[4]["candidates"] == 1361
+
+
+def test_sampler_entries_report_no_overlap_launch(gpu):
+    lib = nb.blib()
+    rep = nb._new_report()
+    rep.overlap_launches = 7
+    n, codes, nrm = ctypes.c_size_t(), ctypes.c_void_p(), ctypes.c_void_p()
+    rc = lib.svob_surface_leaves_ex(0, nb.CUSTOM1, 5, None, ctypes.byref(rep), ctypes.byref(n), ctypes.byref(codes),
+                                    ctypes.byref(nrm))
+    lib.svob_free_ptr(codes)
+    lib.svob_free_ptr(nrm)
+    assert rc == 0 and n.value > 0 and rep.slabs == 1 and rep.overlap_launches == 0 and rep.size == ctypes.sizeof(rep)
+
+
+# ------------------------------------------------------------------ 13. 512^3: spanning triangles across the natural launch edge
+def regrowth_model(counts, cap):
+    """mesh_leaves_gpu's capacity bookkeeping over the slabs' leaf counts: (relaunches, final capacity)."""
+    relaunches = 0
+    for cnt in counts:
+        if cnt > cap:
+            cap = int(cnt * 1.25) + 1024
+            relaunches += 1
+    return relaunches, cap
+
+
+SPAN9_LIMITS = [None, {"launch_candidates": 10_000_019}, {"slab_rows": 100}, {"list_capacity": 1000},
+                {"slab_rows": 100, "list_capacity": 1000}]
+
+
+@pytest.mark.parametrize("limits", SPAN9_LIMITS, ids=lambda d: "+".join(d) if d else "default")
+def test_span9_equals_the_banded_reference(gpu, limits):
+    """Four spanning triangles, a sliver and a near-planar one at 512^3, 4.0e8 candidates.  At the default limits
+    the owner grid is one slab of 512 MiB and the 2^28 limit ends the first launch inside the fourth spanning
+    triangle's box (tests/test_voxelize.py proves that from the boxes): two launches, no knob.  A prime limit, six
+    slabs with a partial last one and a list that regrows give the same bytes."""
+    n, lim = 512, limits or {}
+    want = vu.band_reference("span9")
+    got = leaves("span9", limits=limits)
+    same_leaves(got, want, "span9")
+    assert got[5] == want[4], (got[5], want[4])
+    rep = got[4]
+    rows = lim.get("slab_rows", n)
+    totals = slab_totals("span9", rows)
+    assert rep["slab_rows"] == rows and rep["slabs"] == len(totals) == -(-n // rows)
+    assert rep["overlap_launches"] == launches(totals, lim.get("launch_candidates", 1 << 28))
+    z = vz.leaf_xyz(want[0])[:, 2].astype(np.int64)
+    relaunches, cap = regrowth_model(np.bincount(z // rows, minlength=len(totals)).tolist(),
+                                     lim.get("list_capacity", max(1 << 20, 4 * n * n)))
+    assert (rep["relaunches"], rep["list_capacity"], rep["normals_regrown"]) == (relaunches, cap, int(len(z) > cap))
+    if limits is None:
+        assert rep["slabs"] == 1 and rep["overlap_launches"] == 2 and totals[0] > 1 << 28
+    if "launch_candidates" in lim:
+        assert rep["overlap_launches"] == 41
+    if "slab_rows" in lim:
+        assert rep["slabs"] == 6 and n % rows == 12 and all(t > 0 for t in totals)
+    if "list_capacity" in lim:
+        assert rep["relaunches"] >= 1
+        assert rep["normals_regrown"] == (1 if "slab_rows" in lim else 0)   # one slab regrows past all leaves at once
+
+
+# ------------------------------------------------------------------ 14. 512^3: an ordinary closed mesh, all 9 bits of every coordinate
+def test_ico6_9_leaves_equal_the_banded_reference(gpu):
+    want = vu.band_reference("ico6_9")
+    got = leaves("ico6_9")
+    same_leaves(got, want, "ico6_9")
+    assert got[5] == want[4] and got[4]["slabs"] == 1 and got[4]["overlap_launches"] == 1
+    xyz = vz.leaf_xyz(want[0])
+    assert len(vu.mesh("ico6_9")[1]) == 81920 and len(want[0]) > 500000
+    assert np.all(xyz.max(0) >= 256) and np.all(xyz.min(0) < 256) and int(want[0].max()) >> 26 == 1
+
+
+@pytest.fixture(scope="module")
+def ico6_9_pool(gpu):
+    pos, tri, depth = vu.mesh("ico6_9")
+    return nb.build_mesh_svo(pos, tri, depth + 1, colors=vu.vertex_colors(pos), prefer_v1=False)
+
+
+def test_ico6_9_pool_equals_layout_of_the_banded_leaves(gpu, ico6_9_pool):
+    pos, tri, depth = vu.mesh("ico6_9")
+    codes, nrm, col, _, stats = vu.band_reference("ico6_9")
+    xyz = vz.leaf_xyz(codes)
+    assert ico6_9_pool.format == 2
+    assert pool_bytes(ico6_9_pool) == pool_bytes(nb.build_from_leaves(depth, xyz, nrm, col, prefer_v1=False))
+    got, rep, st = nb.build_mesh_svo(pos, tri, depth + 1, colors=vu.vertex_colors(pos), report=True)
+    assert pool_bytes(got) == pool_bytes(nb.build_from_leaves(depth, xyz, nrm, col))
+    assert got.n_leaves == len(codes) and st == stats and rep["overlap_launches"] == 1
+
+
+def test_render_of_the_ico6_9_pool_equals_the_oracle(gpu, oracle_mod, ico6_9_pool):
+    w, h = 96, 64
+    cam = overview_camera()
+    m = RaytracingMaster(device=0, capacity_nodes=len(ico6_9_pool))
+    try:
+        m.SetSVOBuffer(ico6_9_pool)
+        m.UpdateShaderParameters(cam, w, h)
+        rgba, hits = m.Render(w, h)
+    finally:
+        m.close()
+    c2w, inv_proj = cam.uniforms(w, h)
+    ocam = oracle_mod.make_camera(c2w, inv_proj, (0.5, 0.5), main_light())
+    ref_hits, ref_rgba, _ = oracle_mod.render(qu.oracle_svo(oracle_mod, ico6_9_pool), ocam, w, h)
+    assert np.count_nonzero(ref_hits["flags"] & 1) >= 100
     assert hits.reshape(-1).tobytes() == ref_hits.tobytes()
     np.testing.assert_allclose(rgba.reshape(-1, 4), ref_rgba, rtol=1e-5, atol=1e-6)
 

@@ -54,7 +54,10 @@ def test_header_compiles_in_c_and_matches_ctypes(tmp_path):
                    ' offsetof(svob_mesh_stats, outside) == 16 && offsetof(svob_mesh_stats, candidates) == 24 &&'
                    ' offsetof(svob_mesh_stats, overlaps) == 32, "svob_mesh_stats layout");\n'
                    '_Static_assert(SVOB_MESH_FLIP_WINDING == 1, "flag");\n'
-                   '_Static_assert(sizeof(svob_limits) == 32 && sizeof(svob_report) == 32, "the older structs stay");\n'
+                   '_Static_assert(sizeof(svob_limits) == 40 && offsetof(svob_limits, max_blocks) == 28 &&'
+                   ' offsetof(svob_limits, launch_candidates) == 32, "svob_limits: the older fields stay, one appended");\n'
+                   '_Static_assert(sizeof(svob_report) == 40 && offsetof(svob_report, list_capacity) == 24 &&'
+                   ' offsetof(svob_report, overlap_launches) == 32, "svob_report: the older fields stay, one appended");\n'
                    'int main(void){return 0;}\n')
     subprocess.run(["gcc", "-std=c11", "-Wall", "-Werror", "-c", "-I", os.path.join(ROOT, "include"), str(src),
                     "-o", str(tmp_path / "a.o")], check=True)
@@ -64,6 +67,9 @@ def test_header_compiles_in_c_and_matches_ctypes(tmp_path):
                                            "colors")] == [0, 4, 8, 16, 24, 32, 40]
     assert [getattr(S, k).offset for k in ("size", "reserved", "degenerate", "outside", "candidates", "overlaps")] == \
         [0, 4, 8, 16, 24, 32]
+    assert ctypes.sizeof(nb._Limits) == 40 and nb._Limits.max_blocks.offset == 28 and nb._Limits.launch_candidates.offset == 32
+    assert ctypes.sizeof(nb._Report) == 40 and nb._Report.list_capacity.offset == 24 and nb._Report.overlap_launches.offset == 32
+    assert "launch_candidates" in nb.LIMIT_FIELDS and nb.MESH_REPORT_FIELDS == nb.REPORT_FIELDS + ("overlap_launches",)
 
 
 def _call(native, mesh, max_level=5, limits=None, stats=None, report=None):
@@ -169,6 +175,29 @@ def test_mesh_struct_is_versioned_by_size(native):
     assert np.array_equal(svo.attachments, ref.attachments)
 
 
+def test_launch_limit_and_report_field_without_gpu(native):
+    """svob_limits.launch_candidates takes every value, and svob_report.overlap_launches is written (0: a mesh
+    without triangles launches nothing) -- unless the caller's report is the older, shorter struct."""
+    m, keep = _raw_mesh(np.zeros((0, 3), f32), np.zeros((0, 3), np.uint32))
+    for value in (0, 1, 63, 2 ** 28, 2 ** 64 - 1):
+        lim = nb._Limits(size=ctypes.sizeof(nb._Limits), launch_candidates=value)
+        rep = nb._new_report()
+        rep.overlap_launches = rep.slabs = 7
+        rc, res = _call(native, m, limits=ctypes.byref(lim), report=rep)
+        assert rc == 0, native.svob_last_error()
+        assert (rep.size, rep.slabs, rep.overlap_launches, rep.reserved2) == (ctypes.sizeof(nb._Report), 0, 0, 0)
+        native.svob_free(ctypes.byref(res))
+    old = nb._Report(size=nb._Report.overlap_launches.offset, slabs=7, overlap_launches=7)
+    rc, res = _call(native, m, report=old)
+    assert rc == 0 and (old.size, old.slabs, old.overlap_launches) == (32, 0, 7)
+    native.svob_free(ctypes.byref(res))
+    with pytest.raises(nb.SvoError):
+        nb.mesh_leaves(GOOD_POS, [(0, 1, 2)], 5, limits={"launch_candidate": 5})
+    out = nb.mesh_leaves(np.zeros((0, 3), f32), np.zeros((0, 3), np.uint32), 5, limits={"launch_candidates": 5}, report=True)
+    assert out[4] == {"slabs": 0, "slab_rows": 16, "relaunches": 0, "normals_regrown": 0,
+                      "list_capacity": 1 << 20, "overlap_launches": 0}
+
+
 def test_bindings_declare_meshes():
     text = open(os.path.join(ROOT, "unity", "RaytracingMasterNative.cs")).read()
     assert re.search(r"\[DllImport\(Builder\)\] public static extern int svob_build_mesh\(", text)
@@ -251,6 +280,60 @@ def test_driver_under_sanitizers(tmp_path):
     for name in ("all_edges", "soup", "empty"):
         pos, tri, depth = vu.mesh(name)
         same_leaves(run_driver(exe, pos, tri, depth, vu.vertex_colors(pos)), vu.reference(name), name)
+    cases = decode_cases()
+    assert np.array_equal(run_decode(exe, cases)[:, :3], decode_expected(cases))
+
+
+# ------------------------------------------------------------------ 2b. the candidate decode
+def run_decode(exe, cases):
+    """The driver's --decode mode on cases [(local, bx, by)]: uint32 [m, 9] = candidate_voxel's, the 64-bit
+    form's and (where it applies) the 32-bit form's (x, y, z)."""
+    d = exe.parent
+    with open(d / "decode_in.bin", "wb") as f:
+        f.write(np.array([len(cases)], np.uint64).tobytes())
+        f.write(np.array(cases, np.uint64).reshape(-1, 3).tobytes())
+    subprocess.run([str(exe), "--decode", str(d / "decode_in.bin"), str(d / "decode_out.bin")], check=True)
+    return np.fromfile(d / "decode_out.bin", np.uint32).reshape(len(cases), 9)
+
+
+def decode_cases():
+    """(local, bx, by): local at 0, around 2^32, at 2^40 + 12345 and at the last candidate of a box of 1 and of
+    2^21 planes, for widths and depths whose plane stays below 2^32 (local alone selects the 64-bit form), and for
+    bx = by = 2^20 (the plane selects it)."""
+    sides = (1, 2, 3, 511, 512, 65535)
+    boxes = [(bx, by) for bx in sides for by in sides] + [(1 << 20, 1 << 20)]
+    out = []
+    for bx, by in boxes:
+        for local in (0, 2 ** 32 - 1, 2 ** 32, 2 ** 32 + 1, 2 ** 40 + 12345, bx * by - 1, bx * by * (1 << 21) - 1):
+            out.append((local, bx, by))
+    return out
+
+
+def decode_expected(cases):
+    """Python integers: x first, then y, then z; z modulo 2^32 (a candidate of a box has z below 2^21)."""
+    return np.array([(local % bx, local // bx % by, local // (bx * by) % 2 ** 32) for local, bx, by in cases], np.uint32)
+
+
+def test_candidate_voxel_equals_python_integers(driver):
+    """candidate_voxel (svo_voxelize.h, called by mesh_overlap_kernel) against Python integers.  Both forms are
+    evaluated wherever the 32-bit one applies, and agree; the 64-bit form is selected by local alone and by the
+    plane alone."""
+    cases = decode_cases()
+    want = decode_expected(cases)
+    got = run_decode(driver, cases)
+    narrow = np.array([local < 2 ** 32 and bx * by < 2 ** 32 for local, bx, by in cases])
+    by_local = [c for c in cases if c[0] >= 2 ** 32 and c[1] * c[2] < 2 ** 32]
+    by_plane = [c for c in cases if c[0] < 2 ** 32 and c[1] * c[2] >= 2 ** 32]
+    assert narrow.sum() >= 36 * 3 and len(by_local) >= 36 * 3 and len(by_plane) == 2
+    assert max(bx * by for _, bx, by in cases if (bx, by) != (1 << 20, 1 << 20)) < 2 ** 32
+    for k, c in enumerate(cases):
+        assert got[k, :3].tolist() == want[k].tolist(), (c, got[k].tolist(), want[k].tolist())
+        assert got[k, 3:6].tolist() == want[k].tolist(), ("64-bit form", c)
+        if narrow[k]:
+            assert got[k, 6:].tolist() == want[k].tolist(), ("32-bit form", c)
+    # inside a box every coordinate stays inside it: the last candidate of bx x by x 2^21 is its far corner
+    last = [k for k, (local, bx, by) in enumerate(cases) if local == bx * by * (1 << 21) - 1]
+    assert all(got[k, :3].tolist() == [cases[k][1] - 1, cases[k][2] - 1, (1 << 21) - 1] for k in last) and len(last) == 37
 
 
 def test_edge_cases_are_what_the_rule_says():
@@ -310,6 +393,103 @@ def test_rule_brackets_the_float64_overlap(name):
         xyz = vz.leaf_xyz(codes).astype(np.float64) + 0.5
         out = xyz - np.array([0.5013, 0.4987, 0.5021]) * (1 << depth)
         assert np.all((vu.reference(name)[1] * out).sum(1) > 0)
+
+
+# ------------------------------------------------------------------ 3b. 512^3: the banded reference
+@pytest.mark.parametrize("name", vu.MAIN + vu.MORE + vu.EDGES)
+def test_band_reference_equals_reference(name):
+    """What licenses the band: on every mesh that fits a dense grid, the rule evaluated on the band of each
+    triangle's plane alone (large boxes, by Tri) or by the array form of Tri (small boxes) gives voxelize.voxelize's
+    leaves, owners, normals, colours and statistics byte for byte."""
+    variants = [(True, False)] + ([(False, True)] if name in ("ico2", "all_edges", "bigtiny") else [])
+    for colors, flip in variants:
+        want, got = vu.reference(name, colors, flip), vu.band_reference(name, colors, flip)
+        same_leaves(got, want, name)
+        assert got[4] == want[4], name
+        assert all(a.dtype == b.dtype and a.shape == b.shape for a, b in zip(got[:4], want[:4]) if b is not None)
+    cand = vu.batch_of(name).candidates()
+    if name == "bigtiny":   # both paths: the spanning triangle's band through Tri, the 2,000 small boxes as arrays
+        assert cand[0] > vu.SMALL_BOX and np.all(cand[1:] <= vu.SMALL_BOX) and np.all(cand[1:] > 0)
+        t = vz.Tri(vu.mesh(name)[0][:3], 64)
+        assert len(vu.band_cells(t, 64)) < 0.2 * t.candidates()   # and the band does prune
+    tris = vz.setup(*vu.mesh(name)) if name in ("soup", "all_edges") else []
+    assert [t.candidates() for t in tris] == cand[:len(tris)].tolist()
+
+
+def test_span9_crosses_the_launch_limit_inside_a_triangle():
+    """The conditions span9 is built for, from the rule's boxes alone: its four spanning triangles hold more than
+    2^28 candidates (three do not), and candidate 2^28 of the only slab lies strictly inside one triangle's range,
+    so the default launch limit ends one launch and starts the next in the middle of a box."""
+    pos, tri, depth = vu.mesh("span9")
+    assert depth == 9 and len(tri) == 2006 and list(vu.SPAN9_NAMED.values()) == [0, 2004, 2005]
+    cand = vu.batch_of("span9").candidates()
+    for k in (0, 1, 2, 3, 2004, 2005):
+        assert vz.Tri(pos[tri[k]], 512).candidates() == cand[k]
+    assert cand[:4].sum() > 2 ** 28 > cand[:3].sum() and 2.9e8 < cand[:4].sum() < 3.1e8
+    ends = np.cumsum(cand)
+    k = int(np.searchsorted(ends, 2 ** 28, side="right"))
+    assert k == 3 and ends[k] - cand[k] < 2 ** 28 < ends[k] - 1
+    assert 2 ** 28 < ends[-1] < 2 * 2 ** 28            # two launches at the default limit
+    assert 512 * 512 * 512 * 4 == 512 << 20            # one slab at the default cell_bytes
+
+
+@pytest.fixture(scope="module")
+def span9_named():
+    """Per named triangle of span9 at 512^3: (Tri, band cells, the rule on them, delta)."""
+    pos, tri, depth = vu.mesh("span9_named")
+    out = {}
+    for k, name in enumerate(vu.SPAN9_NAMED):
+        t = vz.Tri(pos[tri[k]], 1 << depth)
+        cells = vu.band_cells(t, 1 << depth)
+        out[name] = (t, cells, t.overlaps_at(cells), vu.rule_delta(pos, tri[k:k + 1], depth))
+    return out
+
+
+@pytest.mark.parametrize("name", list(vu.SPAN9_NAMED))
+def test_rule_brackets_the_float64_overlap_at_512(span9_named, name):
+    """must <= leaves <= may at 512^3, where delta is ten times what a 64^3 grid can show.  The float64 model is
+    evaluated on the band: outside it a voxel is a whole cell away from every crossing of the plane with its
+    column, which no cube of half extent below 1 reaches; the ring of one more cell around the band is evaluated
+    too and holds no voxel of `may`.  The sliver's bracket holds but says little: its delta of a quarter voxel
+    leaves more voxels undecided than it has leaves, so it is asserted without the 1 % cap."""
+    t, cells, ok, delta = span9_named[name]
+    n = 512
+    v = t.v.astype(np.float64)
+    key = lambda c: (c[:, 2] * n + c[:, 1]) * n + c[:, 0]
+    assert len(np.unique(key(cells))) == len(cells)
+    if name == "near_planar":   # its box is one voxel thick: the band is the box
+        assert len(cells) == t.candidates() and t.bhi[1] == t.blo[1]
+    else:
+        assert len(cells) < 0.05 * t.candidates()
+    grown = vu.band_cells(t, n, grow=1)
+    ring = grown[~np.isin(key(grown), key(cells))]
+    in_box = np.all((ring >= t.blo) & (ring <= t.bhi), axis=1)
+    assert len(ring) > len(cells) / 4 and (in_box.sum() > 1000) == (name != "near_planar")
+    assert not np.any(vu.sat_at(v, ring[in_box] + 0.5, 0.5 + delta))
+    must, may = vu.sat_at(v, cells + 0.5, 0.5 - delta), vu.sat_at(v, cells + 0.5, 0.5 + delta)
+    undecided = int((may & ~must).sum())
+    print(f"{name}: delta {delta:.3g} voxel, candidates {t.candidates()}, band {len(cells)}, leaves {int(ok.sum())}, "
+          f"must {int(must.sum())}, may {int(may.sum())}, undecided {undecided}")
+    assert 0 < delta < 0.5 and ok.sum() > 1000
+    assert not np.any(must & ~may)
+    assert not np.any(must & ~ok), int((must & ~ok).sum())
+    assert not np.any(ok & ~may), int((ok & ~may).sum())
+    if name == "sliver":
+        assert delta > 0.1    # on record: a spanning sliver's bound is weak
+    else:
+        assert delta < 1e-3 and undecided <= 0.01 * ok.sum(), (undecided, int(ok.sum()))
+
+
+def test_header_equals_band_reference_at_512(driver):
+    """The header through g++ on span9's three named triangles at 512^3 -- whole boxes, 1.9e8 candidates, nothing
+    pruned -- gives the banded numpy reference byte for byte: no leaf of the rule lies outside the band, and the
+    coordinates beyond 6 bits, the owners, normals, colours and statistics agree."""
+    pos, tri, depth = vu.mesh("span9_named")
+    want = vu.band_reference("span9_named")
+    got = run_driver(driver, pos, tri, depth, vu.vertex_colors(pos))
+    same_leaves(got, want, "span9_named")
+    assert got[4] == want[4] and want[4]["candidates"] > 1.9e8
+    assert set(want[3].tolist()) == {0, 1, 2} and vz.leaf_xyz(want[0]).max() >= 500
 
 
 # ------------------------------------------------------------------ 4. owner and attribute rules

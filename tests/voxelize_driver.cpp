@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
+#include <string>
 #include <utility>
 #include <vector>
 
@@ -27,7 +28,35 @@ static bool read_vec(FILE *f, std::vector<T> &v, size_t n) {
     return n == 0 || fread(v.data(), sizeof(T), n, f) == n;
 }
 
+// voxelize_driver --decode in.bin out.bin: candidate_voxel on a list of cases.
+// in:  uint64 count, then count x (uint64 local, bx, by), bx and by below 2^32.
+// out: count x 9 uint32: candidate_voxel's (x, y, z), the 64-bit form's, and the 32-bit form's where local and
+//      bx by fit 32 bits (zeros elsewhere).
+static int decode_cases(const char *in, const char *out) {
+    FILE *f = fopen(in, "rb");
+    if (!f) return 2;
+    uint64_t count = 0;
+    if (fread(&count, 8, 1, f) != 1) return 2;
+    std::vector<uint64_t> cases;
+    if (!read_vec(f, cases, 3 * (size_t)count)) return 2;
+    fclose(f);
+    std::vector<uint32_t> res(9 * (size_t)count, 0u);
+    for (size_t k = 0; k < count; ++k) {
+        const uint64_t local = cases[3 * k];
+        const uint32_t bx = (uint32_t)cases[3 * k + 1], by = (uint32_t)cases[3 * k + 2];
+        const uint64_t plane = (uint64_t)bx * by;
+        candidate_voxel(local, bx, by, &res[9 * k]);
+        candidate_voxel_64(local, bx, plane, &res[9 * k + 3]);
+        if (((local | plane) >> 32) == 0) candidate_voxel_32((uint32_t)local, bx, (uint32_t)plane, &res[9 * k + 6]);
+    }
+    FILE *o = fopen(out, "wb");
+    if (!o) return 2;
+    if (count) fwrite(res.data(), 4, res.size(), o);
+    return fclose(o) == 0 ? 0 : 2;
+}
+
 int main(int argc, char **argv) {
+    if (argc == 4 && std::string(argv[1]) == "--decode") return decode_cases(argv[2], argv[3]);
     if (argc != 3) return 2;
     FILE *f = fopen(argv[1], "rb");
     if (!f) return 2;
